@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — queries/sec of the gfx950 pathfinder hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4|c5]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the result line (the
+headline rate, ms_per_step, and the roofline of the timed steps' own launch events).
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+--full adds everything that takes runs of its own: fresh batches timed end to end,
+the CPU baseline and its parity check of the GPU's labels, and the N > 1 gather check.
 
 One "step" = one pass of the hot path over one batch: every query of the
 rank's shard is answered (one single-source solve per unique source, all
@@ -81,10 +88,16 @@ def parse():
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
     ap.add_argument("--queries", type=int, default=0,
                     help="override queries per GPU (c4: the whole batch is this x N)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the end-to-end batches, the CPU baseline with its parity check, and (N > 1) the "
+                         "gather check; off: the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the labels the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-seconds", type=float, default=24.0,
-                    help="CPU-baseline budget (wall seconds, split between the 1-thread and all-threads legs)")
-    ap.add_argument("--e2e-reps", type=int, default=3, help="fresh batches timed end to end (0: skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: CPU-baseline budget (wall seconds, split between the 1-thread and "
+                         "all-threads legs)")
+    ap.add_argument("--e2e-reps", type=int, default=3, help="with --full: fresh batches timed end to end (0: skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--pmc", default="", help="JSON with PMC-derived HBM bytes per launch (profiles/)")
     return ap.parse_args()
 
@@ -308,6 +321,69 @@ def end_to_end(m, grid, params, qpg, seed, max_cmds, reps, pinned=False):
                     "median of reps after one untimed batch (cold_ms: its time)"}
 
 
+DUMP_SEED = 20240  # the sample of a larger output is the same in every run and build
+DUMP_QUERIES = 65536  # labels kept of a query batch
+DUMP_COMMANDS = 262144  # command rows kept of those labels
+DUMP_SOURCES, DUMP_CELLS = 4, 65536  # all destinations: sources and cells kept
+
+
+def dump_outputs(path, plan, all_dst, V):
+    """Writes what `plan`'s last pass computed, as a caller receives it, into `path` as
+    float64 .npy files (every field is an integer below 2^53, so the values are exact);
+    ~32 MB at the most.  A batch larger than the sample is cut to a fixed, seeded choice
+    of its queries (sources and cells), so two builds dump the same entries.
+
+    Query batches (mr_plan_fetch, the rank's query order):
+      queries.npy   (k,)    which queries of the batch the rows below answer
+      results.npy   (k, 5)  legs, money, time_s, n_commands, status of each; a query
+                            without a path has zeros before its status
+      commands.npy  (c, 14) the labels' commands in that order, one row each: the row of
+                            results.npy it belongs to, kind, legs, money, fleetfoot,
+                            time_s, then kind, sub, x, y of its `from` and its `to` cell;
+                            the first DUMP_COMMANDS rows
+    All destinations (mr_sssp_records):
+      sources.npy   (s,)       which of the plan's sources
+      cells.npy     (k,)       which row-major cells
+      records.npy   (s, k, 4)  legs, money, time, via of each (source, cell)"""
+    import ctypes
+
+    import numpy as np
+    from marshrutka_amd.abi import mr_command
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def save(name, a):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    if all_dst:
+        src = np.sort(rng.choice(plan.n, min(plan.n, DUMP_SOURCES), replace=False))
+        cell = np.sort(rng.choice(V, min(V, DUMP_CELLS), replace=False))
+        save("sources", src)
+        save("cells", cell)
+        save("records", np.stack([plan.records(int(i))[cell] for i in src]))
+        return
+    res, pool = plan.fetch_raw()
+    rdt = np.dtype([("legs", "<u4"), ("money", "<u4"), ("time_s", "<i8"), ("n", "<u4"), ("off", "<u4"),
+                    ("status", "<i4"), ("reserved", "<u4")])
+    cdt = np.dtype([("kind", "u1"), ("reserved", "u1", (3,)), ("legs", "<u4"), ("money", "<u4"), ("fleetfoot", "<u4"),
+                    ("time_s", "<i8")] + [(e + f, t) for e in ("from_", "to_")
+                                          for f, t in (("kind", "u1"), ("sub", "u1"), ("x", "<u2"), ("y", "<u2"),
+                                                       ("reserved", "<u2"))])
+    assert rdt.itemsize == ctypes.sizeof(res._type_) and cdt.itemsize == ctypes.sizeof(mr_command)
+    pick = np.sort(rng.choice(plan.n, min(plan.n, DUMP_QUERIES), replace=False))
+    r = np.frombuffer(res, dtype=rdt, count=plan.n)[pick]
+    ok = r["status"] == 0
+    save("queries", pick)
+    save("results", np.stack([np.where(ok, r[f], 0) for f in ("legs", "money", "time_s", "n")] + [r["status"]], axis=1))
+    ncmd = np.where(ok, r["n"], 0).astype(np.int64)
+    row = np.repeat(np.arange(len(pick), dtype=np.int64), ncmd)[:DUMP_COMMANDS]
+    within = np.arange(int(ncmd.sum()), dtype=np.int64)[:DUMP_COMMANDS] - (np.cumsum(ncmd) - ncmd)[row]
+    c = np.frombuffer(pool, dtype=cdt)[r["off"].astype(np.int64)[row] + within]
+    save("commands", np.stack([row] + [c[f] for f in ("kind", "legs", "money", "fleetfoot", "time_s",
+                                                      "from_kind", "from_sub", "from_x", "from_y",
+                                                      "to_kind", "to_sub", "to_x", "to_y")], axis=1))
+
+
 def cpu_model():
     try:
         with open("/proc/cpuinfo") as f:
@@ -489,8 +565,10 @@ def main():
     if dist_on:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plans[(it[0] - 1) % len(plans)], all_dst, wl["size"] ** 2)
     gather_check = None
-    if pipe is not None:
+    if pipe is not None and args.full:
         gather_check = check_gather(pipe, plans[(it[0] - 1) % len(plans)], (it[0] - 1) % len(plans), grid, params,
                                     shards, orders, counts, rows, rw, wpool_cap, rank, world)
     kn = [p_.kernel_ms() for p_ in plans]
@@ -614,16 +692,17 @@ def main():
         out["config"]["shard_ms"] = shard_ms  # shard_by_source over the whole batch (host, untimed)
     if gather_check is not None:
         out["gather_check"] = gather_check
-    if rank == 0 and not all_dst and args.e2e_reps > 0:
+    if rank == 0 and not all_dst and args.full and args.e2e_reps > 0:
         out["end_to_end"] = end_to_end(m, grid, params, qpg, wl["seed"], wl.get("max_cmds", 16), args.e2e_reps)
         # the same with the output arrays page-locked once (mr_host_register)
         out["end_to_end_pinned"] = end_to_end(m, grid, params, qpg, wl["seed"], wl.get("max_cmds", 16), args.e2e_reps,
                                               pinned=True)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and all_dst:
+    cpu_leg = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
+    if cpu_leg and all_dst:
         cb, parity = cpu_baseline_all(m, params, plan, mine, args.cpu_seconds)
         out["cpu_baseline"] = cb
         out["parity"] = parity
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif cpu_leg:
         # the oracle's sample is a prefix of the batch (a few hundred queries at 1025^2):
         # only that prefix becomes Python objects
         from marshrutka_amd.abi import CellIndex, result_from_c

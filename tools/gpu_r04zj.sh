@@ -11,5 +11,5 @@ for q in 5000 20000 40000; do
     env $env timeout -k 10 200 python bench.py --queries $q --steps 20 --warmup 3 --no-cpu-baseline --e2e-reps 0 > $O/b_${q}_$tag.json 2> $O/b_${q}_$tag.err || exit 1
   done
 done
-timeout -k 10 120 python bench.py --workload c2 --steps 50 --warmup 5 --no-cpu-baseline --e2e-reps 3 > $O/b_c2.json 2> $O/b_c2.err || exit 1
-timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --e2e-reps 2 > $O/b_c4.json 2> $O/b_c4.err
+timeout -k 10 120 python bench.py --workload c2 --steps 50 --warmup 5 --full --no-cpu-baseline --e2e-reps 3 > $O/b_c2.json 2> $O/b_c2.err || exit 1
+timeout -k 10 200 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --e2e-reps 2 > $O/b_c4.json 2> $O/b_c4.err

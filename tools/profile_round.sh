@@ -13,7 +13,7 @@ steps() { case $1 in c5) echo 3;; *) echo 20;; esac; }
 qpg() { case $1 in c2) echo 10000;; c3) echo 1024;; c4) echo 1000000;; c5) echo 10000;; esac; }
 for W in $WLS; do
   ST=$(steps $W)
-  timeout -k 10 300 python3 "$R/bench.py" --workload $W --steps $ST --warmup 2 > $O/bench_$W.json 2> $O/bench_$W.err || exit 1
+  timeout -k 10 300 python3 "$R/bench.py" --workload $W --steps $ST --warmup 2 --full > $O/bench_$W.json 2> $O/bench_$W.err || exit 1
   echo "$W bench ok"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt_$W -o run --output-format csv -- python3 "$R/bench.py" --workload $W --steps $ST --warmup 2 --no-cpu-baseline > $O/kt_$W.log 2>&1 || exit 1
   echo "$W kernel trace ok"
