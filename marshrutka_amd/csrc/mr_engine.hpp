@@ -223,6 +223,11 @@ struct KArgs {
     // the certificate's second round (promoted specials, mr_cert_tile.hpp): non-null in the
     // argument block of the round's kernels, which skip the slots with cert_redo[slot] == 0
     uint32_t *cert_redo;
+    // lane plans whose specials' labels do not depend on the source's position (the memo
+    // gate, DESIGN.md section 3a'''): nreg + NS rows of lane_memo_row_words(TM) words
+    // (mr_hub_lane.hpp), built once per (grid, params) by hub_lane_build_kernel and read by
+    // hub_lane_memo_kernel; null: the plan runs hub_lane_kernel
+    uint32_t *lane_memo;
 };
 // cert_redo[slot]: kRedoFill — promoted specials: the closed form again, both checks and the
 // repair; kRedoSweep — specials the last check demoted: the repair from the current words

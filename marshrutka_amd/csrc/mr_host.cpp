@@ -13,6 +13,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <chrono>
 #include <thread>
@@ -50,6 +51,11 @@ int hub_wide_blocks_per_cu(const uint32_t perm[3], uint32_t NS, uint32_t bytes);
 uint32_t hub_lane_entries(uint32_t NS);
 hipError_t launch_hub_lane(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
                            bool nonlin, hipStream_t stream);
+uint32_t lane_memo_words(uint32_t NS, uint32_t nreg);
+hipError_t launch_lane_memo_build(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg,
+                                  hipStream_t stream);
+hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
+                                hipStream_t stream);
 uint32_t hub_group_slots(uint32_t NS, uint32_t G);
 uint32_t lane_blob_build(const SpecialStatic *sp, uint32_t NS, uint32_t nreg, uint32_t TM, uint32_t rgt,
                          uint32_t ff_num, uint32_t ff_den, const uint32_t *near_sp, std::vector<uint32_t> &blob);
@@ -207,6 +213,19 @@ struct mr_grid {
     // wide hub solver without the region table: a special cell's row of {distance, rank}
     // per region, scanned from the boundary cells once per (homeland, cell)
     mutable std::unordered_map<uint32_t, std::vector<uint32_t>> near_sp_cache[4];
+    // lane memo (lane_memo_rows): the specials' tables per SoE region and per special cell,
+    // built on the device once per (device, homeland, HQ cell, params) and shared by the
+    // grid's plans; `gate`: the rows stand for every source (else `why` says what failed)
+    struct LaneMemo {
+        uint32_t *d_rows = nullptr;
+        bool gate = false;
+        std::string why;
+        ~LaneMemo() {
+            if (d_rows) (void)hipFree(d_rows);
+        }
+    };
+    mutable std::mutex memo_mu;
+    mutable std::map<std::string, std::shared_ptr<LaneMemo>> lane_memo;
     // device copies of the region tables, built on first use and shared by the grid's
     // plans (the grid outlives its plans): one per (device, homeland), so a plan never
     // reads a table that lives on another device
@@ -1765,6 +1784,7 @@ struct mr_plan {
     uint32_t *d_near = nullptr, *d_fb = nullptr;
     uint32_t *d_near_sp = nullptr, *d_rb_off = nullptr, *d_rb_cell = nullptr;  // wide hub tables
     uint32_t *d_lane_blob = nullptr;  // lane / group kernels: the plan's LDS block (lane_blob_build)
+    std::shared_ptr<mr_grid::LaneMemo> memo;  // lane memo rows (the grid's; ka.lane_memo when the gate holds)
     uint32_t *d_relist = nullptr;     // lane kernel (Fleetfoot): uncertain sources for hub_kernel (KArgs::relist)
     OutCmd *d_ovf = nullptr;              // command-overflow pool (labels longer than max_cmds)
     // outputs bound with an overflow buffer (a collective gathers them raw): each pass
@@ -2002,6 +2022,110 @@ static bool lane_layout_ok(const HostPlan &hp) {
         if (r != kNone10 && (r < 6 || r >= 6 + kLaneRegs || hp.sp[r].rid == kNone10)) return false;
     }
     return true;
+}
+
+// The lane memo's rows and gate (DESIGN.md section 3a''').  Split a source's own edges into
+// A, the position-independent ones (the d = 0 SoE into its own region's campfire, SHQ,
+// SFm), and B (the walks and the [Std{d}, SoE] pairs with d >= 1).  Every B candidate is
+// componentwise >= the one-leg walk (1 leg, 0 money, 180 s).  Row r is the lane Dijkstra's
+// table for region r with only A offered; if every entry of it is strictly below the
+// one-leg walk in the plan's order, no B candidate changes or ties a label, so the row is
+// the table of every non-special source of the region (uniqueness of the fixed point,
+// DESIGN.md section 2).  A special source has a row of its own, an ordinary solve.  ka: the
+// plan's arguments, complete for a lane launch.  nullptr: a device error.
+static std::shared_ptr<mr_grid::LaneMemo> lane_memo_rows(const mr_grid *g, int dev, const HostPlan &hp, const KArgs &ka,
+                                                         hipStream_t stream) {
+    const uint32_t NS = hp.p.NS, nreg = hp.nreg, nrows = nreg + NS;
+    std::string key(sizeof(DevParams) + 12, '\0');
+    {
+        DevParams kp = hp.p;
+        kp.max_cmds = 0;  // (the rows do not depend on it)
+        const uint32_t tail[3] = {uint32_t(dev), uint32_t(hp.homeland), hp.hq_v};
+        std::memcpy(&key[0], &kp, sizeof(kp));
+        std::memcpy(&key[sizeof(kp)], tail, sizeof(tail));
+    }
+    std::lock_guard<std::mutex> lk(g->memo_mu);
+    auto it = g->lane_memo.find(key);
+    if (it != g->lane_memo.end()) return it->second;
+    auto m = std::make_shared<mr_grid::LaneMemo>();
+    auto keep = [&] {
+        if (g->lane_memo.size() >= 64) g->lane_memo.clear();  // (plans hold their rows themselves)
+        g->lane_memo[key] = m;
+        return m;
+    };
+    if (nreg == 0 || nreg > kLaneRegs || nrows > 64) {
+        m->why = "no SoE regions";
+        return keep();
+    }
+    // a plain cell of every region (any: the A edges do not depend on the position)
+    std::vector<uint32_t> srcs(nrows, kNone32);
+    {
+        const std::vector<uint32_t> &regs = region_list(g, hp.homeland), &near = g->nearest[hp.homeland];
+        uint32_t left = nreg;
+        for (uint32_t v = 0; v < g->V && left; ++v) {
+            if (v == g->vc || near[v] == kNone32) continue;
+            uint32_t r = 0;
+            while (r < nreg && regs[r] != near[v]) ++r;
+            if (r == nreg || srcs[r] != kNone32) continue;
+            bool special = false;
+            for (uint32_t t = 1; t <= NS && !special; ++t) special = hp.sp[t].v == v;
+            if (special) continue;
+            srcs[r] = v;
+            --left;
+        }
+        if (left) {
+            m->why = "a region without a plain cell";
+            return keep();
+        }
+        for (uint32_t t = 1; t <= NS; ++t) srcs[nreg + t - 1] = hp.sp[t].v;
+    }
+    const uint32_t words = lane_memo_words(NS, nreg), rw = words / nrows;
+    std::vector<uint32_t> rows(words);
+    uint32_t *d_src = nullptr;
+    KArgs *d_kb = nullptr;
+    KArgs kb = ka;
+    bool ok = dev_malloc(reinterpret_cast<void **>(&m->d_rows), size_t(words) * 4) == hipSuccess &&
+              dev_malloc(reinterpret_cast<void **>(&d_src), size_t(nrows) * 4) == hipSuccess &&
+              dev_malloc(reinterpret_cast<void **>(&d_kb), sizeof(KArgs)) == hipSuccess;
+    if (ok) {
+        kb.src_v = d_src;
+        kb.n_lane = nrows;
+        kb.lane_memo = m->d_rows;
+        kb.relist = nullptr;
+        kb.dbg = nullptr;
+        ok = hipMemcpy(d_src, srcs.data(), size_t(nrows) * 4, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(d_kb, &kb, sizeof(KArgs), hipMemcpyHostToDevice) == hipSuccess &&
+             launch_lane_memo_build(d_kb, hp.p.perm, NS, nreg, stream) == hipSuccess &&
+             hipStreamSynchronize(stream) == hipSuccess &&
+             hipMemcpy(rows.data(), m->d_rows, size_t(words) * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (d_src) (void)hipFree(d_src);
+    if (d_kb) (void)hipFree(d_kb);
+    if (!ok) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    // the gate: every row certified, every entry of a region's row strictly below the
+    // one-leg walk on the metrics in the plan's order
+    const uint32_t leg[3] = {1u, 0u, 180u};
+    const uint32_t w[3] = {leg[hp.p.perm[0]], leg[hp.p.perm[1]], leg[hp.p.perm[2]]};
+    m->gate = true;
+    for (uint32_t r = 0; r < nrows && m->gate; ++r) {
+        const uint32_t *row = &rows[size_t(r) * rw];
+        if (row[rw - 1] != 1u) {
+            m->gate = false;
+            m->why = "an uncertain row (blockers)";
+        }
+        for (uint32_t t = 1; t <= NS && r < nreg && m->gate; ++t) {
+            const uint32_t *c = row + 4 * t;
+            const bool below = c[0] != w[0] ? c[0] < w[0] : (c[1] != w[1] ? c[1] < w[1] : c[2] < w[2]);
+            if (!below) {
+                m->gate = false;
+                m->why = "a special's label is not below a one-leg walk in this order";
+            }
+        }
+    }
+    return keep();
 }
 
 // sources that would run on the lane kernel (at most kLaneMaxQ queries)
@@ -2441,6 +2565,7 @@ static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *q
     ka.algo = pl->algo;
     ka.dbg = nullptr;
     ka.near = nullptr;
+    ka.lane_memo = nullptr;
     ka.nreg = 0;
     ka.fb_list = nullptr;
     ka.fb_mode = 0;
@@ -2621,6 +2746,27 @@ static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *q
             if (upload(pl->d_lane_blob, blob) != MR_OK) return bail(fail(MR_ERR_DEVICE, "lane tables"));
             ka.lane_blob = reinterpret_cast<const uint4 *>(pl->d_lane_blob);
         }
+    }
+    {
+        // The lane memo (DESIGN.md section 3a'''): where the gate holds, the lane kernel's
+        // sources read their destinations off rows built once per (grid, params).
+        // MR_LANE_MEMO=0: never; =require: plan creation fails where the gate is false
+        // (tests tell the path that ran this way).
+        const char *lm = std::getenv("MR_LANE_MEMO");
+        const bool memo_off = lm && !std::strcmp(lm, "0"), memo_req = lm && !std::strcmp(lm, "require");
+        std::string why = "switched off";
+        if (!memo_off) {
+            if (!hp.hub || !pl->n_lane || pl->lane_g) why = "not a lane plan";
+            else if (hub_lane_entries(NS) != 22) why = "a table of more than 22 entries";
+            else if (hp.nonlin) why = "non-linear run times";
+            else {
+                pl->memo = lane_memo_rows(g, pl->device, hp, ka, pl->stream);
+                if (!pl->memo) return bail(fail(MR_ERR_DEVICE, "lane memo rows"));
+                if (pl->memo->gate) ka.lane_memo = pl->memo->d_rows;
+                else why = pl->memo->why;
+            }
+        }
+        if (memo_req && !ka.lane_memo) return bail(fail(MR_ERR_INVALID_ARG, "MR_LANE_MEMO=require: " + why));
     }
 #ifdef MR_HUBDUMP
     if (const char *e = std::getenv("MR_DEBUG_SRC"))
@@ -2842,8 +2988,13 @@ extern "C" int mr_plan_run(mr_plan *pl, void *stream) {
         e = hipSuccess;
         if (pl->n_lane) {
             const KArgs *la = pl->fb_none && !big ? pl->d_args_lane_last : pl->d_args_lane;
-            e = pl->lane_g ? launch_hub_group(la, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->n_lane, pl->lane_g, pl->hp.nonlin, s)
-                           : launch_hub_lane(la, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->n_lane, pl->hp.nonlin, s);
+            // (a plan whose memo gate held: the destinations only, from the grid's rows)
+            if (pl->lane_g)
+                e = launch_hub_group(la, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->n_lane, pl->lane_g, pl->hp.nonlin, s);
+            else if (pl->ka.lane_memo)
+                e = launch_hub_lane_memo(la, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->n_lane, s);
+            else
+                e = launch_hub_lane(la, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->n_lane, pl->hp.nonlin, s);
         }
         if (e == hipSuccess && big) e = launch_hub_plan(pl, pl->fb_none ? pl->d_args_hub_last : pl->d_args, s);
         // certified fallback: the slots given to the staged sources in source order,

@@ -280,8 +280,24 @@ __device__ __forceinline__ uint32_t ltm3(const LLab &x, const LLab &y) {
     } while (0)
 #endif
 
-template <uint32_t PERM, uint32_t TM, bool NL = false>
+// What a LaneHub instantiation does with a source (lane memo, DESIGN.md section 3a'''):
+//   kLaneSolve  the whole solve: own edges, Dijkstra, certification, destinations
+//   kLaneBuild  the memo rows of a (grid, params): own edges, Dijkstra and certification
+//               of one source per lane, the table written out as a row instead of read
+//               off.  A lane with `aonly` set is offered only the position-independent
+//               own edges (the d = 0 SoE into its own region's campfire, SHQ, SFm): the
+//               table every non-special source of that region shares when the gate
+//               holds (lane_memo_rows, mr_host.cpp)
+//   kLaneMemo   destinations only: the table is the source's memo row (LDS)
+constexpr uint32_t kLaneSolve = 0, kLaneBuild = 1, kLaneMemo = 2;
+// A memo row: entry t's label at words 4 t .. 4 t + 3 (c1, c2, c3, meta; entry 0 is the
+// start label), then {done, bndm, blk, valid}.  Rows 0 .. nreg - 1 are the regions',
+// row nreg + t - 1 is special t's own (an ordinary solve from its cell).
+__host__ __device__ constexpr uint32_t lane_memo_row_words(uint32_t TM) { return 4u * TM + 4u; }
+
+template <uint32_t PERM, uint32_t TM, bool NL = false, uint32_t MODE = kLaneSolve>
 struct LaneHub {
+    static_assert(!(NL && MODE != kLaneSolve), "memo rows: linear run times only");
 #ifdef MR_STAMPS
     unsigned long long lst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lst_last = 0;
 #endif
@@ -306,6 +322,8 @@ struct LaneHub {
     // tentative / settled labels of entries 1..TM-1 (entry 0, the source, is the start label)
     LLab L[TM];
     uint32_t tent = 0, done = 0, wt = 0, bndm = 0, blk = 0;
+    const uint4 *R = nullptr;  // kLaneMemo: this lane's memo row (LDS), read in place of L
+    bool aonly = false;        // kLaneBuild: a region's row (position-independent own edges only)
 
     // ---- metrics in comparator order -------------------------------------------------
     __device__ __forceinline__ static uint32_t pick(uint32_t i, uint32_t legs, uint32_t money, uint32_t time) {
@@ -356,10 +374,22 @@ struct LaneHub {
     __device__ __forceinline__ uint2 near_of(uint32_t p, uint32_t r) const { return p == 0 ? srow[r] : nearS[p * nreg + r]; }
     // entry e's label (run-time e; a select per entry: the rare paths only)
     __device__ __forceinline__ LLab get(uint32_t e) const {
+        if constexpr (MODE == kLaneMemo) {
+            const uint4 q = R[e];
+            return LLab{q.x, q.y, q.z, q.w};
+        }
         LLab r = start();
 #pragma unroll
         for (uint32_t t = 1; t < TM; ++t) ll_sel(vmask(e == t), r, L[t]);
         return r;
+    }
+    // entry t's label where t is a constant of an unrolled loop
+    __device__ __forceinline__ LLab lab(uint32_t t) const {
+        if constexpr (MODE == kLaneMemo) {
+            const uint4 q = R[t];
+            return LLab{q.x, q.y, q.z, q.w};
+        }
+        return L[t];
     }
 
     // ---- commands of a label (rare paths: list compares and output) -----------------
@@ -408,13 +438,17 @@ struct LaneHub {
     const uint2 *HT;     // LDS: the specials' cells by hash (lane_hash)
     uint32_t ht_probes;  // the longest probe sequence in HT
     __device__ __forceinline__ void dump_meta() const {
+        if constexpr (MODE == kLaneMemo) return;  // (the row holds the metas)
         const uint32_t l = lane_id();
         M[mcolumn] = start().m;
         (void)l;
 #pragma unroll
         for (uint32_t t = 1; t < TM; ++t) M[t * mstride + mcolumn] = L[t].m;
     }
-    __device__ __forceinline__ uint32_t meta_of(uint32_t e) const { return M[e * mstride + mcolumn]; }
+    __device__ __forceinline__ uint32_t meta_of(uint32_t e) const {
+        if constexpr (MODE == kLaneMemo) return R[e].w;
+        return M[e * mstride + mcolumn];
+    }
     // the meta copy's layout: entry t of this lane's column at t * mstride + mcolumn (the
     // lane kernel: a column per lane; the group kernel: one per group)
     uint32_t mstride = 64u, mcolumn = 0u;
@@ -881,15 +915,29 @@ struct LaneHub {
     }
 
     // ---- one source per lane ----------------------------------------------------------
-    // returns the records this lane wrote (0 when the source went to the SSSP kernel)
-    __device__ __forceinline__ uint32_t solve(bool have, uint32_t s_idx) {
+    // The phases of a solve: the source's words, its own edges, the Dijkstra over the
+    // specials, the certification of the settled labels, the destinations.  solve() runs
+    // them all; the memo kernels (mr_k_lane_memo.hip) run the first four once per region
+    // and special (kLaneBuild) and the last one per source (kLaneMemo).
+    __device__ __forceinline__ void source_setup(uint32_t s_idx) {
         const DevParams &p = P;
-        const uint32_t NS = p.NS;
         src = a->src_v[s_idx];
         sx = int(src % p.S) - int(p.H);
         sy = int(src / p.S) - int(p.H);
         cell_word(src, sx, sy, ts, src_rk);
         srow = reinterpret_cast<const uint2 *>(a->near) + (unsigned long long)src * nreg;
+    }
+    // returns the records this lane wrote (0 when the source went to the SSSP kernel)
+    __device__ __forceinline__ uint32_t solve(bool have, uint32_t s_idx) {
+        source_setup(s_idx);
+        own_edges(have);
+        dijkstra();
+        if (!have) return 0;
+        return read_off(s_idx, certify());
+    }
+    __device__ __forceinline__ void own_edges(bool have) {
+        const DevParams &p = P;
+        const uint32_t NS = p.NS;
         // the source's own edges, in command-kind order: its start label if it is a
         // special, the walks from it, the SoE edges from its region rows, SHQ, SFm
         // (src/pathfinder.rs:162-178)
@@ -915,7 +963,9 @@ struct LaneHub {
             LLab w = inf();
             if (t != 1) {
                 const uint32_t k = walk_dist(sx, sy, tS.x, tS.y);
-                won = vmask(valid && walks0 && tS.v != src);
+                bool wk = valid && walks0 && tS.v != src;
+                if constexpr (MODE == kLaneBuild) wk = wk && !aonly;  // (a walk: position-dependent)
+                won = vmask(wk);
                 w = opt(won, mk(k, 0, rtime(k), lm_pack(1, 0, 1, kStandard)));
                 consider(c, w);
                 any |= won;
@@ -928,7 +978,8 @@ struct LaneHub {
 #pragma unroll
                 for (uint32_t r = 0; r < kLaneRegs; ++r) ev = rid == r ? rowx[r] : ev;
                 const uint32_t e = reg ? ev : kNone32;
-                const bool on = walks0 && reg && e != kNone32;
+                bool on = walks0 && reg && e != kNone32;
+                if constexpr (MODE == kLaneBuild) on = on && (!aonly || e == 0u);  // (d >= 1: position-dependent)
                 const uint32_t d = on ? e : 0u;
                 const uint32_t om = vmask(on);
                 consider(c, opt(om, mk(d, p.soe_cost, rtime(d),
@@ -951,6 +1002,9 @@ struct LaneHub {
             MR_LANE_FENCE();
         }
         MR_LSTAMP(1);  // (1: the source's own edges)
+    }
+    __device__ __forceinline__ void dijkstra() {
+        const uint32_t NS = P.NS;
         // ---- Dijkstra over the specials, one settle per lane per iteration ----------
         for (uint32_t it = 0; it < NS; ++it) {
             const uint32_t cand = tent & ~done;
@@ -1078,7 +1132,9 @@ struct LaneHub {
             }
             MR_LSTAMP(4);  // (4: the relaxations and their ties)
         }
-        if (!have) return 0;
+    }
+    // true: some settled label is uncertain (the source goes to the fallback)
+    __device__ __forceinline__ bool certify() {
         // ---- certification: with blockers, every settled walk label must be certain ----
         bool unc = false;
         dump_meta();  // (certification and the destinations' command chains)
@@ -1097,6 +1153,12 @@ struct LaneHub {
             }
         }
         MR_LSTAMP(6);  // (6: the certification of settled labels)
+        return unc;
+    }
+    // the source's queries from its settled table; returns the records written
+    __device__ __forceinline__ uint32_t read_off(uint32_t s_idx, bool unc) {
+        const DevParams &p = P;
+        const LLab st0 = start();
         const uint32_t qa = a->q_begin[s_idx], qb = a->q_begin[s_idx + 1];
         const bool fb_sp = unc || a->fb_all;
         // ---- destinations: the source, a special's own label, or the best walk ------------
@@ -1133,7 +1195,8 @@ struct LaneHub {
             for (uint32_t t = 2; t < TM; ++t) {
                 const uint32_t k = walk_dist(spl[t].x, spl[t].y, wx, wy);
                 const uint32_t cm = bitm(bq, t);
-                const LLab c = opt(cm, add(L[t], k, 0, rtime(k), L[t].m));
+                const LLab lt_ = lab(t);
+                const LLab c = opt(cm, add(lt_, k, 0, rtime(k), lt_.m));
 #ifdef MR_LANE_CLASSIC
                 const uint32_t lt = ltm(c, x), gt = ltm(x, c);
                 tie = ~lt & (tie | (cm & ~gt & (1u << t)));
@@ -1182,6 +1245,49 @@ struct LaneHub {
         else if (fallback) push_fallback(a, counter, s_idx, kNone32);
         return fallback ? 0u : qb - qa;
     }
+
+    // ---- memo rows --------------------------------------------------------------------
+    // kLaneBuild: source s_idx solved into row s_idx of a->lane_memo (valid: certified).
+    // Unsettled entries keep c1 = 2^32 - 1: the host's gate reads them as not there.
+    __device__ __forceinline__ void build_row(bool have, uint32_t s_idx, bool region_row) {
+        aonly = region_row;
+        source_setup(s_idx);
+        own_edges(have);
+        dijkstra();
+        if (!have) return;
+        const bool unc = certify();
+        uint4 *o = reinterpret_cast<uint4 *>(a->lane_memo + (unsigned long long)s_idx * lane_memo_row_words(TM));
+        const LLab s0 = start();
+        o[0] = make_uint4(s0.c1, s0.c2, s0.c3, s0.m);
+#pragma unroll
+        for (uint32_t t = 1; t < TM; ++t) o[t] = make_uint4(L[t].c1, L[t].c2, L[t].c3, L[t].m);
+        o[TM] = make_uint4(done, bndm, blk, unc ? 0u : 1u);
+    }
+    // kLaneMemo: the source's queries from its memo row (rows: the plan's rows in LDS) — a
+    // special's own row, else the row of the region the source lies in (distance 0)
+    __device__ __forceinline__ uint32_t memo_solve(uint32_t s_idx, const uint4 *rows) {
+        source_setup(s_idx);
+        uint32_t row = kNone32;
+        {
+            const uint32_t nr = min(nreg, kLaneRegs);
+#pragma unroll
+            for (uint32_t r = kLaneRegs; r-- > 0;) {
+                const uint32_t d = r < nr ? srow[r].x : kNone32;
+                row = d == 0u ? r : row;
+            }
+        }
+        row = ts != kNone10 ? nreg + ts - 1u : row;
+        if (row == kNone32) {  // a plain cell of no region: cannot happen where the gate held
+            push_fallback(a, counter, s_idx, kNone32);
+            return 0;
+        }
+        R = rows + row * (lane_memo_row_words(TM) / 4u);
+        const uint4 h = R[TM];
+        done = h.x;
+        bndm = h.y;
+        blk = h.z;
+        return read_off(s_idx, false);
+    }
 };
 
 // The lane kernels' LDS.  Its first part is a per-plan block the host builds once
@@ -1220,14 +1326,21 @@ __host__ __device__ inline uint32_t lane_lds_total(uint32_t NS, uint32_t nreg, u
 // The lane kernels' workgroup setup: the plan's block copied into LDS (16 B a thread per
 // step; the same block for every workgroup, so after the first ones it comes from L2),
 // and the solver's fields.
-template <uint32_t TM, class Hub>
+// (PAIRS false: the pair table and its row masks, which only the Dijkstra reads, stay out)
+template <uint32_t TM, class Hub, bool PAIRS = true>
 __device__ __forceinline__ void lane_setup(const KArgs *__restrict__ a, char *smem, Hub &H) {
     const uint32_t NS = a->p.NS, nreg = a->nreg;
     {
         const uint4 *blob = a->lane_blob;
         uint4 *dst = reinterpret_cast<uint4 *>(smem);
         const uint32_t n16 = lane_blob_bytes(NS, nreg, TM) / 16u;
-        for (uint32_t i = threadIdx.x; i < n16; i += kBS) dst[i] = blob[i];
+        if constexpr (PAIRS) {
+            for (uint32_t i = threadIdx.x; i < n16; i += kBS) dst[i] = blob[i];
+        } else {
+            const uint32_t p0 = lane_off_pt(NS, nreg) / 16u, p1 = lane_off_hash(NS, nreg, TM) / 16u;
+            for (uint32_t i = threadIdx.x; i < p0; i += kBS) dst[i] = blob[i];
+            for (uint32_t i = p1 + threadIdx.x; i < n16; i += kBS) dst[i] = blob[i];
+        }
     }
     __syncthreads();
     H.a = a;

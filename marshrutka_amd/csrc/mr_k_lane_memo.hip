@@ -1,0 +1,124 @@
+// mr_k_lane_memo.hip — the lane memo (DESIGN.md section 3a'''): under a comparator order
+// that leads with Legs, with caravans and Scrolls of Escape on, the labels of the specials
+// depend on a non-special source only through its SoE region.  hub_lane_build_kernel
+// solves them once per region and once per special cell (LaneHub<.., kLaneBuild>, one
+// wave); hub_lane_memo_kernel is hub_lane_kernel without the own edges and the Dijkstra:
+// each lane takes its source's row and reads its destinations off it.  The host decides
+// per (grid, params) whether the rows stand for every source (lane_memo_rows, mr_host.cpp).
+#include "mr_hub_lane.hpp"
+
+namespace mr {
+
+// one wave: lane l solves source l of a->src_v (the first a->nreg of them region
+// representatives, then the specials' cells) into row l of a->lane_memo
+template <uint32_t PERM, uint32_t TM>
+__global__ __launch_bounds__(kBS, lane_waves(TM)) void hub_lane_build_kernel(const KArgs *__restrict__ a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    LaneHub<PERM, TM, false, kLaneBuild> H;
+    lane_setup<TM>(a, smem, H);
+    H.MC = reinterpret_cast<uint32_t *>(smem + lane_lds_total(a->p.NS, a->nreg, TM)) + (threadIdx.x >> 6) * (TM * 64u);
+    const uint32_t s_idx = threadIdx.x, n = a->n_lane;
+    const bool have = s_idx < n;
+    // (whole waves: the Dijkstra's wave-wide tests want every lane in)
+    if (__any(have)) H.build_row(have, have ? s_idx : (n ? n - 1 : 0), s_idx < a->nreg);
+}
+
+// the memo kernel's LDS: the lane kernels' block (its pair table left out), then the rows
+__host__ __device__ inline uint32_t lane_memo_lds_bytes(uint32_t NS, uint32_t nreg, uint32_t TM) {
+    return lane_blob_bytes(NS, nreg, TM) + (nreg + NS) * lane_memo_row_words(TM) * 4u;
+}
+
+// hub_lane_kernel's launch geometry, source order and end-of-pass bookkeeping.  Four
+// waves per SIMD: a lane holds no table, only the destination it is reading off.
+template <uint32_t PERM, uint32_t TM>
+__global__ __launch_bounds__(kBS, 4) void hub_lane_memo_kernel(const KArgs *__restrict__ a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    LaneHub<PERM, TM, false, kLaneMemo> H;
+#ifdef MR_STAMPS
+    H.lst_last = __builtin_amdgcn_s_memtime();
+#endif
+    const uint32_t NS = a->p.NS, nreg = a->nreg;
+    uint4 *rows = reinterpret_cast<uint4 *>(smem + lane_blob_bytes(NS, nreg, TM));
+    {  // (before lane_setup's barrier; L2-resident after the first workgroups)
+        const uint4 *g = reinterpret_cast<const uint4 *>(a->lane_memo);
+        const uint32_t n16 = (nreg + NS) * (lane_memo_row_words(TM) / 4u);
+        for (uint32_t i = threadIdx.x; i < n16; i += kBS) rows[i] = g[i];
+    }
+    lane_setup<TM, decltype(H), false>(a, smem, H);
+#ifdef MR_STAMPS
+    {
+        const unsigned long long now_ = __builtin_amdgcn_s_memtime();
+        H.lst[0] += now_ - H.lst_last;  // (0: the table copy)
+        H.lst_last = now_;
+    }
+#endif
+    const uint32_t s_idx = (blockIdx.x * (kBS / 64) + (threadIdx.x >> 6)) * 64u + lane_id();
+    uint32_t written = 0;
+    if (s_idx < a->n_lane) written = H.memo_solve(s_idx, rows);
+#ifdef MR_STAMPS
+    {
+        const unsigned long long now_ = __builtin_amdgcn_s_memtime();
+        H.lst[5] += now_ - H.lst_last;  // (5: the source's row and the destinations)
+        if (a->dbg && lane_id() == 0) {
+            unsigned long long *h = a->dbg + (unsigned long long)a->dbg_blocks * 10 + 9;
+            atomicAdd(h, 1ull);
+            for (int i = 0; i < 6; ++i) atomicAdd(h + 1 + i, H.lst[i]);
+            atomicAdd(h - 2, H.lst[6]);
+        }
+    }
+#endif
+    __shared__ uint32_t wsum;
+    if (threadIdx.x == 0) wsum = 0;
+    __syncthreads();
+    if (written) atomicAdd(&wsum, written);
+    __syncthreads();
+    if (threadIdx.x == 0) finish_launch(a, wsum);
+}
+
+// The gate holds where every special is reached at 0 legs under a Legs-first order (perms
+// 5 and 7).  The other orders are instantiated too, so that the gate alone decides.
+#define MR_MEMO_FN(NAME)                                                             \
+    static const void *NAME##_fn(uint32_t perm) {                                    \
+        switch (perm) {                                                              \
+            case 5: return reinterpret_cast<const void *>(&NAME<5, 22>);             \
+            case 7: return reinterpret_cast<const void *>(&NAME<7, 22>);             \
+            case 11: return reinterpret_cast<const void *>(&NAME<11, 22>);           \
+            case 15: return reinterpret_cast<const void *>(&NAME<15, 22>);           \
+            case 19: return reinterpret_cast<const void *>(&NAME<19, 22>);           \
+            case 21: return reinterpret_cast<const void *>(&NAME<21, 22>);           \
+            default: return nullptr;                                                 \
+        }                                                                            \
+    }
+MR_MEMO_FN(hub_lane_build_kernel)
+MR_MEMO_FN(hub_lane_memo_kernel)
+#undef MR_MEMO_FN
+
+uint32_t hub_lane_lds_bytes(uint32_t NS, uint32_t nreg);
+
+// words of one memo row and rows of a plan (22-entry tables only)
+uint32_t lane_memo_words(uint32_t NS, uint32_t nreg) { return (nreg + NS) * lane_memo_row_words(22); }
+
+// d_args: the plan's arguments with src_v = the rows' sources (nreg region
+// representatives, then the NS specials' cells), n_lane = nreg + NS, lane_memo = the rows
+hipError_t launch_lane_memo_build(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg,
+                                  hipStream_t stream) {
+    if (NS + 1 > 22 || nreg + NS > 64) return hipErrorInvalidValue;
+    const void *fn = hub_lane_build_kernel_fn(perm[0] * 9 + perm[1] * 3 + perm[2]);
+    if (!fn) return hipErrorInvalidValue;
+    const uint32_t bytes = hub_lane_lds_bytes(NS, nreg);
+    if (bytes > 64u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
+    void *args[] = {const_cast<KArgs **>(&d_args)};
+    return hipLaunchKernel(fn, dim3(1), dim3(kBS), args, bytes, stream);
+}
+
+hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
+                                hipStream_t stream) {
+    const void *fn = hub_lane_memo_kernel_fn(perm[0] * 9 + perm[1] * 3 + perm[2]);
+    if (!fn || NS + 1 > 22) return hipErrorInvalidValue;
+    const uint32_t bytes = lane_memo_lds_bytes(NS, nreg, 22);
+    const uint32_t waves = (n_lane + 63u) / 64u, blocks = (waves + 3u) / 4u;
+    void *args[] = {const_cast<KArgs **>(&d_args)};
+    return hipLaunchKernel(fn, dim3(blocks ? blocks : 1u), dim3(kBS), args, bytes, stream);
+}
+
+}  // namespace mr
