@@ -337,6 +337,11 @@ double mr_plan_kernel_ms(mr_plan *plan, uint32_t *n_launches);
  * per element type) and every calling thread's grouping scratch (about 20 B per query of
  * that thread's largest batch; a plan being created keeps its own until it returns). */
 void mr_cache_trim(void);
+/* Diagnostics: the cache-managed device blocks that live objects (plans, calls in
+ * progress) hold right now: their number and the sum of their size classes in bytes.
+ * Blocks the cache keeps for reuse and the grids' tables are not counted.  Either
+ * pointer may be NULL; without a device both are 0. */
+void mr_cache_live(uint64_t *blocks, uint64_t *bytes);
 /* Page-locks [p, p + bytes) of caller memory (hipHostRegister) that mr_plan_fetch then
  * fills by direct DMA instead of through the engine's pinned stage and a host copy: for
  * a caller that reuses its fetch buffers batch after batch.  mr_host_unregister(p)

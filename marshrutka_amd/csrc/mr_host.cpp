@@ -24,10 +24,7 @@
 #include "../../include/marshrutka_pf.h"
 #include "mr_engine.hpp"
 #include "mr_pool.hpp"
-
-// hipMalloc for the grid's long-lived device tables: on out-of-memory the plan block
-// cache (below) is trimmed and the allocation retried once
-static hipError_t dev_malloc(void **p, size_t bytes);
+#include "mr_devmem.hpp"
 
 namespace mr {
 uint32_t lds_bytes(uint32_t NS, uint32_t V, bool grid_in_lds, uint32_t algo);
@@ -118,6 +115,23 @@ static int fail(int code, const std::string &msg) {
     g_last_error = msg;
     return code;
 }
+
+// MR_* switches read in more than one place, each parsed here.  They are read at every
+// call: the tests flip them between plans of one process.
+static bool env_is(const char *name, const char *value) {
+    const char *e = std::getenv(name);
+    return e && !std::strcmp(e, value);
+}
+enum class AlgoEnv { unset, sssp, generic };
+static AlgoEnv env_algo() {  // MR_ALGO
+    return env_is("MR_ALGO", "generic") ? AlgoEnv::generic : (env_is("MR_ALGO", "sssp") ? AlgoEnv::sssp : AlgoEnv::unset);
+}
+static bool env_zero(const char *name) {  // set to a number that is 0
+    const char *e = std::getenv(name);
+    return e && std::atoi(e) == 0;
+}
+static bool env_fallback_all() { return std::getenv("MR_HUB_FALLBACK_ALL") != nullptr; }  // tests: every source falls back
+static bool env_host_decode() { return env_is("MR_HOST_DECODE", "1"); }                   // the host decoder fetches
 
 // [0, n) in `parts` near-equal ranges: range p is [chunk_lo(n, parts, p), chunk_lo(n, parts, p + 1))
 static inline uint32_t chunk_lo(uint32_t n, uint32_t parts, uint32_t p) { return uint32_t(uint64_t(n) * p / parts); }
@@ -217,44 +231,30 @@ struct mr_grid {
     // built on the device once per (device, homeland, HQ cell, params) and shared by the
     // grid's plans; `gate`: the rows stand for every source (else `why` says what failed)
     struct LaneMemo {
-        uint32_t *d_rows = nullptr;
+        DevBuf<uint32_t> d_rows;
         bool gate = false;
         std::string why;
-        ~LaneMemo() {
-            if (d_rows) (void)hipFree(d_rows);
-        }
     };
     mutable std::mutex memo_mu;
     mutable std::map<std::string, std::shared_ptr<LaneMemo>> lane_memo;
     // device copies of the region tables, built on first use and shared by the grid's
     // plans (the grid outlives its plans): one per (device, homeland), so a plan never
     // reads a table that lives on another device
-    mutable std::map<std::pair<int, int>, uint32_t *> d_near;
+    mutable std::map<std::pair<int, int>, DevBuf<uint32_t>> d_near;
     // CellIndex of each rank, built on first use by a wire fetch (idx_of_rank)
     mutable std::vector<mr_cell_index> idx_rank_h;
     // device copies shared by the grid's plans on one device (the first plan's): the rank
     // tables, and per (query homeland, HQ cell) the special / region word of every cell
     // (sinfo: it depends on the special order, fixed by those two)
     mutable int d_dev = -1;
-    mutable uint32_t *d_rank = nullptr, *d_rank_inv = nullptr;
+    mutable DevBuf<uint32_t> d_rank, d_rank_inv;
     struct SinfoDev {
         uint32_t homeland, hq_v;
-        uint32_t *d;
-        uint2 *cell;  // {sinfo, rank} per cell
+        DevBuf<uint32_t> d;
+        DevBuf<uint2> cell;  // {sinfo, rank} per cell
     };
     mutable std::vector<SinfoDev> d_sinfo;
-    mutable mr_cell_index *d_idx_rank = nullptr;  // device fetch: the CellIndex of every rank
-    ~mr_grid() {
-        if (d_idx_rank) (void)hipFree(d_idx_rank);
-        for (auto &kv : d_near)
-            if (kv.second) (void)hipFree(kv.second);
-        for (uint32_t *p : {d_rank, d_rank_inv})
-            if (p) (void)hipFree(p);
-        for (const SinfoDev &e : d_sinfo) {
-            (void)hipFree(e.d);
-            (void)hipFree(e.cell);
-        }
-    }
+    mutable DevBuf<mr_cell_index> d_idx_rank;  // device fetch: the CellIndex of every rank
     int32_t gx(uint32_t v) const { return int32_t(v % S) - int32_t(H); }
     int32_t gy(uint32_t v) const { return int32_t(v / S) - int32_t(H); }
     // The geometric layout (checked at creation): homeland cell (h, x, y) at vertex
@@ -408,6 +408,180 @@ static bool grid_fast_layout(mr_grid *g, const mr_cell *cells) {
     return true;
 }
 
+// Grid creation's generic path: the checks cell by cell with a hash map of the indices
+// (and their error messages), the layout's unit steps, the ranks by sorting
+static int grid_generic_layout(mr_grid *g, const mr_cell *cells) {
+    const uint32_t n = g->V;
+    g->fast = g->exact = false;
+    g->campfires.clear();
+    g->index.reserve(n * 2);
+    for (uint32_t i = 0; i < n; ++i) {
+        mr_cell_index c = cells[i].index;
+        // MapGrid::parse builds every index canonically (src/index.rs:419-431)
+        c = build_index(c);
+        if (!canonical(c) || cells[i].poi > MR_POI_FORUM || cells[i].index.reserved)
+            return fail(MR_ERR_INVALID_GRID, "invalid cell index or poi at cell " + std::to_string(i));
+        if (!g->index.emplace(ci_key(c), i).second)
+            return fail(MR_ERR_INVALID_GRID, "duplicate cell index at cell " + std::to_string(i));
+        g->idx[i] = c;
+        g->poi[i] = cells[i].poi;
+    }
+    uint32_t vc;
+    if (!g->find(ci_make(MR_CELL_CENTER, 0, 0, 0), vc) || g->gx(vc) != 0 || g->gy(vc) != 0)
+        return fail(MR_ERR_INVALID_GRID, "Center missing or not at (0,0) (src/grid.rs:122-133)");
+    g->vc = vc;
+    // the index adjacency must be the geometric 4-neighbourhood
+    std::vector<uint64_t> a, b;
+    const int S_ = int(g->S);
+    for (uint32_t v = 0; v < n; ++v) {
+        const mr_cell_index &c = g->idx[v];
+        if ((c.kind == MR_CELL_HOMELAND && (c.x > g->H || c.y > g->H)) || (c.kind == MR_CELL_BORDER && c.x > g->H))
+            return fail(MR_ERR_INVALID_GRID, "cell index outside the homeland size");
+        index_neighbours(c, int(g->H), a);
+        b.clear();
+        int x = int(v % g->S), y = int(v / g->S);
+        if (x > 0) b.push_back(ci_key(g->idx[v - 1]));
+        if (x + 1 < S_) b.push_back(ci_key(g->idx[v + 1]));
+        if (y > 0) b.push_back(ci_key(g->idx[v - g->S]));
+        if (y + 1 < S_) b.push_back(ci_key(g->idx[v + g->S]));
+        std::sort(b.begin(), b.end());
+        if (a != b)
+            return fail(MR_ERR_INVALID_GRID, "cell labels are not a consistent 4-grid at cell " + std::to_string(v));
+    }
+    // the layout's unit steps per homeland and border (find()'s arithmetic path)
+    if (g->H >= 2) {
+        bool ok = true;
+        for (int h = 0; h < 4 && ok; ++h) {
+            uint32_t v11, v21, v12, vb;
+            ok = g->find(ci_make(MR_CELL_HOMELAND, uint8_t(h), 1, 1), v11) &&
+                 g->find(ci_make(MR_CELL_HOMELAND, uint8_t(h), 2, 1), v21) &&
+                 g->find(ci_make(MR_CELL_HOMELAND, uint8_t(h), 1, 2), v12) && g->find(build_border(h, 1), vb);
+            if (!ok) break;
+            g->ux[h] = int64_t(v21) - int64_t(v11);
+            g->uy[h] = int64_t(v12) - int64_t(v11);
+            g->ub[h] = int64_t(vb) - int64_t(vc);
+            ok = int64_t(v11) == int64_t(vc) + g->ux[h] + g->uy[h];
+        }
+        g->fast = ok;
+        // every cell where the formula puts it: find() may then trust the formula
+        bool all = ok;
+        for (uint32_t v = 0; v < n && all; ++v) {
+            const mr_cell_index &c = g->idx[v];
+            int64_t w = -1;
+            if (c.kind == MR_CELL_CENTER) w = vc;
+            else if (c.kind == MR_CELL_HOMELAND) w = int64_t(vc) + c.x * g->ux[c.sub] + c.y * g->uy[c.sub];
+            else if (c.kind == MR_CELL_BORDER) w = int64_t(vc) + c.x * g->ub[c.sub];
+            all = w == int64_t(v);
+        }
+        g->exact = all;
+    }
+    // rank = position in the derived Ord of CellIndex (src/index.rs:41-46)
+    {
+        std::vector<std::pair<uint64_t, uint32_t>> keys(n);
+        for (uint32_t v = 0; v < n; ++v) keys[v] = {ci_key(g->idx[v]), v};
+        std::sort(keys.begin(), keys.end());
+        g->rank.resize(n);
+        g->rank_inv.resize(n);
+        for (uint32_t r = 0; r < n; ++r) {
+            g->rank[keys[r].second] = r;
+            g->rank_inv[r] = keys[r].second;
+        }
+        for (uint32_t r = 0; r < n; ++r)
+            if (g->poi[keys[r].second] == MR_POI_CAMPFIRE) g->campfires.push_back(keys[r].second);
+        bool std_ok = true;
+        for (uint32_t v = 0; v < n && std_ok; ++v) std_ok = g->rank[v] == std_rank(g->gx(v), g->gy(v), g->H);
+        g->rank_std = std_ok && !std::getenv("MR_RANK_TABLE");  // (tests: force the table)
+    }
+    return MR_OK;
+}
+
+// nearest campfire per homeland (src/grid.rs:134-230, 297-325): the argmin of
+// (Manhattan distance, |x|!=|y|, |x|+|y|, |x|, |y|) over the homeland's Homeland-indexed
+// campfires (the reference's projections give the same, tests/test_oracle_kat.py).
+// Along one row y the distance to campfire f is x - fx + |y - fy| for fx <= x and
+// fx - x + |y - fy| for fx >= x, so the best campfire at x is the better of a prefix
+// minimum of (|y - fy| - fx, key) over the campfires left of x and a suffix minimum of
+// (fx + |y - fy|, key) over those right of it: O(S + campfires) a row, rows on the
+// host threads.
+static void grid_nearest_campfires(mr_grid *g) {
+    const uint32_t n = g->V;
+    struct Cf {
+        int64_t fx, fy;
+        uint64_t key;
+        uint32_t v;
+    };
+    std::vector<Cf> cfs[4];
+    for (uint32_t v : g->campfires) {
+        const mr_cell_index &c = g->idx[v];
+        if (c.kind != MR_CELL_HOMELAND) continue;
+        const int64_t fx = int64_t(v % g->S), fy = int64_t(v / g->S);
+        const uint64_t ax = uint64_t(std::abs(g->gx(v))), ay = uint64_t(std::abs(g->gy(v)));
+        cfs[c.sub].push_back(Cf{fx, fy, (uint64_t(ax != ay) << 62) | ((ax + ay) << 40) | (ax << 20) | ay, v});
+    }
+    for (int h = 0; h < 4; ++h) {
+        std::sort(cfs[h].begin(), cfs[h].end(), [](const Cf &p, const Cf &q) { return p.fx < q.fx; });
+        g->nearest[h].assign(n, kNone32);
+    }
+    const uint32_t S = g->S;
+    HostPool &pool = HostPool::get();
+    const uint32_t parts = std::max(1u, std::min(pool.size() * 4, S / 16u));
+    pool.run(parts, [&](uint32_t pt) {
+        std::vector<std::pair<int64_t, uint64_t>> suf;
+        std::vector<uint32_t> sufi;
+        for (uint32_t y = chunk_lo(S, parts, pt); y < chunk_lo(S, parts, pt + 1); ++y)
+            for (int h = 0; h < 4; ++h) {
+                const std::vector<Cf> &cf = cfs[h];
+                const size_t k = cf.size();
+                // suffix minima of (fx + |y - fy|, key) over the campfires sorted by fx
+                suf.resize(k + 1);
+                sufi.resize(k + 1);
+                suf[k] = {INT64_MAX, ~0ull};
+                sufi[k] = kNone32;
+                for (size_t i = k; i-- > 0;) {
+                    const std::pair<int64_t, uint64_t> c{cf[i].fx + std::abs(int64_t(y) - cf[i].fy), cf[i].key};
+                    if (c < suf[i + 1]) {
+                        suf[i] = c;
+                        sufi[i] = cf[i].v;
+                    } else {
+                        suf[i] = suf[i + 1];
+                        sufi[i] = sufi[i + 1];
+                    }
+                }
+                std::pair<int64_t, uint64_t> pre{INT64_MAX, ~0ull};  // (|y - fy| - fx, key), fx <= x
+                uint32_t prei = kNone32;
+                size_t j = 0;  // first campfire with fx > x
+                uint32_t *out = &g->nearest[h][size_t(y) * S];
+                for (uint32_t x = 0; x < S; ++x) {
+                    while (j < k && cf[j].fx <= int64_t(x)) {
+                        const std::pair<int64_t, uint64_t> c{std::abs(int64_t(y) - cf[j].fy) - cf[j].fx, cf[j].key};
+                        if (c < pre) {
+                            pre = c;
+                            prei = cf[j].v;
+                        }
+                        ++j;
+                    }
+                    // right of x: the campfires from the first with fx >= x (fx == x is in both)
+                    size_t jj = j;
+                    while (jj > 0 && cf[jj - 1].fx == int64_t(x)) --jj;
+                    std::pair<int64_t, uint64_t> best{INT64_MAX, ~0ull};
+                    uint32_t bi = kNone32;
+                    if (prei != kNone32) {
+                        best = {pre.first + int64_t(x), pre.second};
+                        bi = prei;
+                    }
+                    if (sufi[jj] != kNone32) {
+                        const std::pair<int64_t, uint64_t> c{suf[jj].first - int64_t(x), suf[jj].second};
+                        if (c < best) {
+                            best = c;
+                            bi = sufi[jj];
+                        }
+                    }
+                    out[x] = bi;
+                }
+            }
+    });
+}
+
 extern "C" int mr_grid_create(const mr_cell *cells, uint32_t n, mr_grid **out) {
     if (!cells || !out) return fail(MR_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
@@ -416,206 +590,29 @@ extern "C" int mr_grid_create(const mr_cell *cells, uint32_t n, mr_grid **out) {
     if (s * s != n) return fail(MR_ERR_INVALID_GRID, "map grid is not square (src/grid.rs:60-63)");
     if (s < 3 || s % 2 == 0) return fail(MR_ERR_INVALID_GRID, "square size must be odd and >= 3");
     if (s > 65535) return fail(MR_ERR_LIMIT, "square size above 65535");
-    auto g = new mr_grid();
+    std::unique_ptr<mr_grid> g(new mr_grid());
     g->S = uint32_t(s);
     g->H = g->S / 2;
     g->V = n;
     g->idx.resize(n);
     g->poi.resize(n);
-    // the standard layout in any orientation: the fast path; anything else, the checks
-    // cell by cell with a hash map of the indices (and their error messages)
+    // the standard layout in any orientation: the fast path; anything else, the generic one
     const double tg0 = timing_on() ? now_ms() : 0.0;
-    if (!grid_fast_layout(g, cells)) {
-        g->fast = g->exact = false;
-        g->campfires.clear();
-        g->index.reserve(n * 2);
-        for (uint32_t i = 0; i < n; ++i) {
-            mr_cell_index c = cells[i].index;
-            // MapGrid::parse builds every index canonically (src/index.rs:419-431)
-            c = build_index(c);
-            if (!canonical(c) || cells[i].poi > MR_POI_FORUM || cells[i].index.reserved) {
-                delete g;
-                return fail(MR_ERR_INVALID_GRID, "invalid cell index or poi at cell " + std::to_string(i));
-            }
-            if (!g->index.emplace(ci_key(c), i).second) {
-                delete g;
-                return fail(MR_ERR_INVALID_GRID, "duplicate cell index at cell " + std::to_string(i));
-            }
-            g->idx[i] = c;
-            g->poi[i] = cells[i].poi;
-        }
-        uint32_t vc;
-        if (!g->find(ci_make(MR_CELL_CENTER, 0, 0, 0), vc) || g->gx(vc) != 0 || g->gy(vc) != 0) {
-            delete g;
-            return fail(MR_ERR_INVALID_GRID, "Center missing or not at (0,0) (src/grid.rs:122-133)");
-        }
-        g->vc = vc;
-        // the index adjacency must be the geometric 4-neighbourhood
-        std::vector<uint64_t> a, b;
-        const int S_ = int(g->S);
-        for (uint32_t v = 0; v < n; ++v) {
-            const mr_cell_index &c = g->idx[v];
-            if ((c.kind == MR_CELL_HOMELAND && (c.x > g->H || c.y > g->H)) || (c.kind == MR_CELL_BORDER && c.x > g->H)) {
-                delete g;
-                return fail(MR_ERR_INVALID_GRID, "cell index outside the homeland size");
-            }
-            index_neighbours(c, int(g->H), a);
-            b.clear();
-            int x = int(v % g->S), y = int(v / g->S);
-            if (x > 0) b.push_back(ci_key(g->idx[v - 1]));
-            if (x + 1 < S_) b.push_back(ci_key(g->idx[v + 1]));
-            if (y > 0) b.push_back(ci_key(g->idx[v - g->S]));
-            if (y + 1 < S_) b.push_back(ci_key(g->idx[v + g->S]));
-            std::sort(b.begin(), b.end());
-            if (a != b) {
-                delete g;
-                return fail(MR_ERR_INVALID_GRID, "cell labels are not a consistent 4-grid at cell " + std::to_string(v));
-            }
-        }
-        // the layout's unit steps per homeland and border (find()'s arithmetic path)
-        if (g->H >= 2) {
-            bool ok = true;
-            for (int h = 0; h < 4 && ok; ++h) {
-                uint32_t v11, v21, v12, vb;
-                ok = g->find(ci_make(MR_CELL_HOMELAND, uint8_t(h), 1, 1), v11) &&
-                     g->find(ci_make(MR_CELL_HOMELAND, uint8_t(h), 2, 1), v21) &&
-                     g->find(ci_make(MR_CELL_HOMELAND, uint8_t(h), 1, 2), v12) && g->find(build_border(h, 1), vb);
-                if (!ok) break;
-                g->ux[h] = int64_t(v21) - int64_t(v11);
-                g->uy[h] = int64_t(v12) - int64_t(v11);
-                g->ub[h] = int64_t(vb) - int64_t(vc);
-                ok = int64_t(v11) == int64_t(vc) + g->ux[h] + g->uy[h];
-            }
-            g->fast = ok;
-            // every cell where the formula puts it: find() may then trust the formula
-            bool all = ok;
-            for (uint32_t v = 0; v < n && all; ++v) {
-                const mr_cell_index &c = g->idx[v];
-                int64_t w = -1;
-                if (c.kind == MR_CELL_CENTER) w = vc;
-                else if (c.kind == MR_CELL_HOMELAND) w = int64_t(vc) + c.x * g->ux[c.sub] + c.y * g->uy[c.sub];
-                else if (c.kind == MR_CELL_BORDER) w = int64_t(vc) + c.x * g->ub[c.sub];
-                all = w == int64_t(v);
-            }
-            g->exact = all;
-        }
-        // rank = position in the derived Ord of CellIndex (src/index.rs:41-46)
-        {
-            std::vector<std::pair<uint64_t, uint32_t>> keys(n);
-            for (uint32_t v = 0; v < n; ++v) keys[v] = {ci_key(g->idx[v]), v};
-            std::sort(keys.begin(), keys.end());
-            g->rank.resize(n);
-            g->rank_inv.resize(n);
-            for (uint32_t r = 0; r < n; ++r) {
-                g->rank[keys[r].second] = r;
-                g->rank_inv[r] = keys[r].second;
-            }
-            for (uint32_t r = 0; r < n; ++r)
-                if (g->poi[keys[r].second] == MR_POI_CAMPFIRE) g->campfires.push_back(keys[r].second);
-            bool std_ok = true;
-            for (uint32_t v = 0; v < n && std_ok; ++v) std_ok = g->rank[v] == std_rank(g->gx(v), g->gy(v), g->H);
-            g->rank_std = std_ok && !std::getenv("MR_RANK_TABLE");  // (tests: force the table)
-        }
-    }
-    // nearest campfire per homeland (src/grid.rs:134-230, 297-325): the argmin of
-    // (Manhattan distance, |x|!=|y|, |x|+|y|, |x|, |y|) over the homeland's Homeland-indexed
-    // campfires (the reference's projections give the same, tests/test_oracle_kat.py).
-    // Along one row y the distance to campfire f is x - fx + |y - fy| for fx <= x and
-    // fx - x + |y - fy| for fx >= x, so the best campfire at x is the better of a prefix
-    // minimum of (|y - fy| - fx, key) over the campfires left of x and a suffix minimum of
-    // (fx + |y - fy|, key) over those right of it: O(S + campfires) a row, rows on the
-    // host threads.
+    if (!grid_fast_layout(g.get(), cells))
+        if (int st = grid_generic_layout(g.get(), cells)) return st;
     for (int h = 0; h < 4; ++h) {
         bool any = false;
         for (uint32_t v : g->campfires) any = any || (g->idx[v].kind == MR_CELL_HOMELAND && g->idx[v].sub == h);
-        if (!any) {
-            delete g;
+        if (!any)
             // MapGrid::parse reaches unreachable!() in this case (src/grid.rs:209)
             return fail(MR_ERR_INVALID_GRID, "a homeland has no campfire (the reference panics, src/grid.rs:209)");
-        }
     }
     const double tg1 = timing_on() ? now_ms() : 0.0;
-    {
-        struct Cf {
-            int64_t fx, fy;
-            uint64_t key;
-            uint32_t v;
-        };
-        std::vector<Cf> cfs[4];
-        for (uint32_t v : g->campfires) {
-            const mr_cell_index &c = g->idx[v];
-            if (c.kind != MR_CELL_HOMELAND) continue;
-            const int64_t fx = int64_t(v % g->S), fy = int64_t(v / g->S);
-            const uint64_t ax = uint64_t(std::abs(g->gx(v))), ay = uint64_t(std::abs(g->gy(v)));
-            cfs[c.sub].push_back(Cf{fx, fy, (uint64_t(ax != ay) << 62) | ((ax + ay) << 40) | (ax << 20) | ay, v});
-        }
-        for (int h = 0; h < 4; ++h) {
-            std::sort(cfs[h].begin(), cfs[h].end(), [](const Cf &p, const Cf &q) { return p.fx < q.fx; });
-            g->nearest[h].assign(n, kNone32);
-        }
-        const uint32_t S = g->S;
-        HostPool &pool = HostPool::get();
-        const uint32_t parts = std::max(1u, std::min(pool.size() * 4, S / 16u));
-        pool.run(parts, [&](uint32_t pt) {
-            std::vector<std::pair<int64_t, uint64_t>> suf;
-            std::vector<uint32_t> sufi;
-            for (uint32_t y = chunk_lo(S, parts, pt); y < chunk_lo(S, parts, pt + 1); ++y)
-                for (int h = 0; h < 4; ++h) {
-                    const std::vector<Cf> &cf = cfs[h];
-                    const size_t k = cf.size();
-                    // suffix minima of (fx + |y - fy|, key) over the campfires sorted by fx
-                    suf.resize(k + 1);
-                    sufi.resize(k + 1);
-                    suf[k] = {INT64_MAX, ~0ull};
-                    sufi[k] = kNone32;
-                    for (size_t i = k; i-- > 0;) {
-                        const std::pair<int64_t, uint64_t> c{cf[i].fx + std::abs(int64_t(y) - cf[i].fy), cf[i].key};
-                        if (c < suf[i + 1]) {
-                            suf[i] = c;
-                            sufi[i] = cf[i].v;
-                        } else {
-                            suf[i] = suf[i + 1];
-                            sufi[i] = sufi[i + 1];
-                        }
-                    }
-                    std::pair<int64_t, uint64_t> pre{INT64_MAX, ~0ull};  // (|y - fy| - fx, key), fx <= x
-                    uint32_t prei = kNone32;
-                    size_t j = 0;  // first campfire with fx > x
-                    uint32_t *out = &g->nearest[h][size_t(y) * S];
-                    for (uint32_t x = 0; x < S; ++x) {
-                        while (j < k && cf[j].fx <= int64_t(x)) {
-                            const std::pair<int64_t, uint64_t> c{std::abs(int64_t(y) - cf[j].fy) - cf[j].fx, cf[j].key};
-                            if (c < pre) {
-                                pre = c;
-                                prei = cf[j].v;
-                            }
-                            ++j;
-                        }
-                        // right of x: the campfires from the first with fx >= x (fx == x is in both)
-                        size_t jj = j;
-                        while (jj > 0 && cf[jj - 1].fx == int64_t(x)) --jj;
-                        std::pair<int64_t, uint64_t> best{INT64_MAX, ~0ull};
-                        uint32_t bi = kNone32;
-                        if (prei != kNone32) {
-                            best = {pre.first + int64_t(x), pre.second};
-                            bi = prei;
-                        }
-                        if (sufi[jj] != kNone32) {
-                            const std::pair<int64_t, uint64_t> c{suf[jj].first - int64_t(x), suf[jj].second};
-                            if (c < best) {
-                                best = c;
-                                bi = sufi[jj];
-                            }
-                        }
-                        out[x] = bi;
-                    }
-                }
-        });
-    }
+    grid_nearest_campfires(g.get());
     if (timing_on())
         std::fprintf(stderr, "[mr] grid_create V=%u: layout+ranks %.2f ms, nearest campfires %.2f ms (%s path)\n", n,
                      tg1 - tg0, now_ms() - tg1, g->exact ? "fast" : "generic");
-    *out = g;
+    *out = g.release();
     return MR_OK;
 }
 
@@ -697,7 +694,7 @@ static const uint32_t *region_table_device(const mr_grid *g, int h, const uint32
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     std::lock_guard<std::mutex> lk(g->near_mu);
     auto it = g->d_near.find({dev, h});
-    if (it != g->d_near.end()) return it->second;
+    if (it != g->d_near.end()) return it->second.get();
     const double t0 = now_ms();
     const uint32_t V = g->V, S = g->S, nreg = uint32_t(regs.size());
     std::unordered_map<uint32_t, uint16_t> rid;
@@ -722,33 +719,28 @@ static const uint32_t *region_table_device(const mr_grid *g, int h, const uint32
             }
         });
     }
-    uint32_t *d = nullptr;
-    uint16_t *d_reg = nullptr;
-    void *d_axis = nullptr, *d_seg = nullptr;
+    DevBuf<uint32_t> d;
+    DevBuf<uint16_t> d_reg;
+    DevBuf<uint64_t> d_axis, d_seg;
     hipStream_t st = nullptr;
     // (MR_REGION_SERIAL=1: the serial kernels, A/B)
     static const bool serial = std::getenv("MR_REGION_SERIAL") != nullptr;
     const uint64_t segw = serial ? 0 : region_table_seg_words(S, nreg);
-    bool ok = nreg > 0 && dev_malloc(reinterpret_cast<void **>(&d), size_t(V) * nreg * 8) == hipSuccess &&
-              dev_malloc(reinterpret_cast<void **>(&d_reg), size_t(V) * 2) == hipSuccess &&
-              dev_malloc(&d_axis, size_t(2) * S * nreg * 8) == hipSuccess &&
-              (!segw || dev_malloc(&d_seg, size_t(segw) * 8) == hipSuccess) &&
+    bool ok = nreg > 0 && d.alloc(size_t(V) * nreg * 2, DevMem::direct) == hipSuccess &&
+              d_reg.alloc(V, DevMem::direct) == hipSuccess &&
+              d_axis.alloc(size_t(2) * S * nreg, DevMem::direct) == hipSuccess &&
+              (!segw || d_seg.alloc(segw, DevMem::direct) == hipSuccess) &&
               hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
-              hipMemcpyAsync(d_reg, reg.data(), size_t(V) * 2, hipMemcpyHostToDevice, st) == hipSuccess &&
-              region_table_build(d_reg, d_rank, S, nreg, d, d_axis, d_seg, st) == hipSuccess &&
+              hipMemcpyAsync(d_reg.get(), reg.data(), size_t(V) * 2, hipMemcpyHostToDevice, st) == hipSuccess &&
+              region_table_build(d_reg.get(), d_rank, S, nreg, d.get(), d_axis.get(), d_seg.get(), st) == hipSuccess &&
               hipStreamSynchronize(st) == hipSuccess;
     if (st) (void)hipStreamDestroy(st);
-    if (d_reg) (void)hipFree(d_reg);
-    if (d_axis) (void)hipFree(d_axis);
-    if (d_seg) (void)hipFree(d_seg);
     if (!ok) {
         (void)hipGetLastError();
-        if (d) (void)hipFree(d);
         return nullptr;
     }
-    g->d_near[{dev, h}] = d;
     g->region_ms[h] = now_ms() - t0;
-    return d;
+    return (g->d_near[{dev, h}] = std::move(d)).get();
 }
 
 // Rows of the region table for the plan's specials (t = 1 .. NS) into near_sp
@@ -1123,8 +1115,7 @@ static int build_plan(const mr_grid *g, const mr_params *prm, const mr_query *qs
     bool linear = p.ff_num == p.ff_den, nonlin_ok = !linear;
     if (const char *e = std::getenv("MR_HUB_NONLIN"))
         if (!std::strcmp(e, "0")) nonlin_ok = false;
-    if (const char *e = std::getenv("MR_ALGO"))
-        if (!std::strcmp(e, "sssp") || !std::strcmp(e, "generic")) linear = nonlin_ok = false;
+    if (env_algo() != AlgoEnv::unset) linear = nonlin_ok = false;
     size_t nregs = 0;
     for (uint32_t v : g->campfires)
         if (g->idx[v].kind == MR_CELL_HOMELAND && g->idx[v].sub == prm->homeland) ++nregs;
@@ -1367,19 +1358,9 @@ static std::vector<uint2> build_cell(const mr_grid *g, const std::vector<uint32_
 // The grid's device rank tables (rank, rank_inv), uploaded on the first device that asks
 // (the caller holds near_mu); false on an upload error.
 static bool grid_rank_upload(const mr_grid *g, int dev) {
-    auto up = [](uint32_t *&d, const std::vector<uint32_t> &h) {
-        if (dev_malloc(reinterpret_cast<void **>(&d), std::max<size_t>(h.size(), 1) * 4) != hipSuccess) return false;
-        if (!h.empty() && hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            d = nullptr;
-            return false;
-        }
-        return true;
-    };
-    if (!up(g->d_rank, g->rank)) return false;
-    if (!up(g->d_rank_inv, g->rank_inv)) {
-        (void)hipFree(g->d_rank);
-        g->d_rank = nullptr;
+    if (upload(g->d_rank, g->rank, DevMem::direct) != hipSuccess) return false;
+    if (upload(g->d_rank_inv, g->rank_inv, DevMem::direct) != hipSuccess) {
+        g->d_rank.reset();
         return false;
     }
     g->d_dev = dev;
@@ -1390,193 +1371,31 @@ static bool grid_rank_upload(const mr_grid *g, int dev) {
 static const uint32_t *grid_rank_device(const mr_grid *g, int dev) {
     std::lock_guard<std::mutex> lk(g->near_mu);
     if (g->d_dev == -1 && !grid_rank_upload(g, dev)) return nullptr;
-    return g->d_dev == dev ? g->d_rank : nullptr;
+    return g->d_dev == dev ? g->d_rank.get() : nullptr;
 }
 
 static bool grid_tables(const mr_grid *g, int dev, const HostPlan &hp, uint32_t *&rank, uint32_t *&rank_inv,
                         uint32_t *&sinfo, uint2 *&cell) {
     std::lock_guard<std::mutex> lk(g->near_mu);
     if (g->d_dev != -1 && g->d_dev != dev) return false;
-    auto up = [](uint32_t *&d, const std::vector<uint32_t> &h) {
-        if (dev_malloc(reinterpret_cast<void **>(&d), std::max<size_t>(h.size(), 1) * 4) != hipSuccess) return false;
-        if (!h.empty() && hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            d = nullptr;
-            return false;
-        }
-        return true;
-    };
     if (g->d_dev == -1 && !grid_rank_upload(g, dev)) return false;
-    uint32_t *ds = nullptr;
-    uint2 *dc = nullptr;
+    const mr_grid::SinfoDev *hit = nullptr;
     for (const mr_grid::SinfoDev &e : g->d_sinfo)
-        if (e.homeland == hp.homeland && e.hq_v == hp.hq_v) {
-            ds = e.d;
-            dc = e.cell;
-        }
-    if (!ds) {
+        if (e.homeland == hp.homeland && e.hq_v == hp.hq_v) hit = &e;
+    if (!hit) {
         if (g->d_sinfo.size() >= 8) return false;
         const std::vector<uint32_t> si = build_sinfo(g, hp);
-        if (!up(ds, si)) return false;
-        const std::vector<uint2> ce = build_cell(g, si);
-        if (dev_malloc(reinterpret_cast<void **>(&dc), std::max<size_t>(ce.size(), 1) * sizeof(uint2)) != hipSuccess) {
-            (void)hipFree(ds);
+        mr_grid::SinfoDev e{hp.homeland, hp.hq_v, {}, {}};
+        if (upload(e.d, si, DevMem::direct) != hipSuccess || upload(e.cell, build_cell(g, si), DevMem::direct) != hipSuccess)
             return false;
-        }
-        if (!ce.empty() && hipMemcpy(dc, ce.data(), ce.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(ds);
-            (void)hipFree(dc);
-            return false;
-        }
-        g->d_sinfo.push_back(mr_grid::SinfoDev{hp.homeland, hp.hq_v, ds, dc});
+        g->d_sinfo.push_back(std::move(e));
+        hit = &g->d_sinfo.back();
     }
-    rank = g->d_rank;
-    rank_inv = g->d_rank_inv;
-    sinfo = ds;
-    cell = dc;
+    rank = g->d_rank.get();
+    rank_inv = g->d_rank_inv.get();
+    sinfo = hit->d.get();
+    cell = hit->cell.get();
     return true;
-}
-
-// Plan buffers come from a cache of freed device blocks (size classes per device: powers
-// of two up to 64 MiB, 64 MiB steps above): a plan for each fresh batch then costs no
-// hipMalloc / hipFree (tens of microseconds each, milliseconds for large blocks).  A
-// block returns to the cache when its plan is destroyed, after mr_plan_destroy has
-// waited for the plan's work; the cache keeps up to 16 GiB and is emptied before a
-// hipMalloc that would otherwise fail.
-struct BlockCache {
-    std::mutex mu;
-    std::unordered_map<void *, std::pair<int, size_t>> live;  // block -> (device, class bytes)
-    std::unordered_map<uint64_t, std::vector<void *>> free;   // (device, class) -> blocks
-    size_t cached = 0;
-};
-static BlockCache &block_cache() {
-    static BlockCache *c = new BlockCache();  // never destroyed: plans may outlive static destructors
-    return *c;
-}
-static size_t size_class(size_t b) {
-    constexpr size_t kBig = size_t(64) << 20;
-    if (b > kBig) return (b + kBig - 1) / kBig * kBig;
-    size_t c = 256;
-    while (c < b) c <<= 1;
-    return c;
-}
-static uint64_t cache_key(int dev, size_t cls) { return (uint64_t(cls) << 8) | uint64_t(dev & 0xFF); }
-static void trim_cache(int dev) {  // hipFree every cached block of `dev` (caller holds the lock)
-    BlockCache &c = block_cache();
-    for (auto it = c.free.begin(); it != c.free.end(); ++it) {
-        if (int(it->first & 0xFF) != (dev & 0xFF)) continue;
-        for (void *q : it->second) {
-            (void)hipFree(q);
-            c.cached -= size_t(it->first >> 8);
-        }
-        it->second.clear();
-    }
-}
-static hipError_t pmalloc(void **p, size_t bytes) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const size_t cls = size_class(std::max<size_t>(bytes, 1));
-    BlockCache &c = block_cache();
-    std::lock_guard<std::mutex> lk(c.mu);
-    auto it = c.free.find(cache_key(dev, cls));
-    if (it != c.free.end() && !it->second.empty()) {
-        *p = it->second.back();
-        it->second.pop_back();
-        c.cached -= cls;
-        c.live[*p] = {dev, cls};
-        return hipSuccess;
-    }
-    hipError_t e = hipMalloc(p, cls);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        trim_cache(dev);
-        e = hipMalloc(p, cls);
-    }
-    if (e == hipSuccess) c.live[*p] = {dev, cls};
-    return e;
-}
-static void pfree(void *p) {
-    if (!p) return;
-    BlockCache &c = block_cache();
-    std::lock_guard<std::mutex> lk(c.mu);
-    auto it = c.live.find(p);
-    if (it == c.live.end()) {
-        (void)hipFree(p);
-        return;
-    }
-    const int dev = it->second.first;
-    const size_t cls = it->second.second;
-    c.live.erase(it);
-    if (c.cached + cls > (size_t(16) << 30)) {
-        (void)hipFree(p);
-        return;
-    }
-    c.free[cache_key(dev, cls)].push_back(p);
-    c.cached += cls;
-}
-static void trim_cache_all() {
-    BlockCache &c = block_cache();
-    std::lock_guard<std::mutex> lk(c.mu);
-    for (auto &kv : c.free) {
-        for (void *q : kv.second) {
-            (void)hipFree(q);
-            c.cached -= size_t(kv.first >> 8);
-        }
-        kv.second.clear();
-    }
-}
-
-// Plan streams come from a per-device pool as well: a destroyed plan (which waited for
-// its work) returns its streams, and the next plan takes them without hipStreamCreate.
-struct StreamPool {
-    std::mutex mu;
-    std::vector<std::pair<int, hipStream_t>> free;
-};
-static StreamPool &stream_pool() {
-    static StreamPool *p = new StreamPool();
-    return *p;
-}
-static hipError_t pstream_create(hipStream_t *s) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        StreamPool &p = stream_pool();
-        std::lock_guard<std::mutex> lk(p.mu);
-        for (size_t i = p.free.size(); i-- > 0;)
-            if (p.free[i].first == dev) {
-                *s = p.free[i].second;
-                p.free.erase(p.free.begin() + long(i));
-                return hipSuccess;
-            }
-    }
-    return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-}
-static void pstream_release(hipStream_t s) {
-    if (!s) return;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    StreamPool &p = stream_pool();
-    std::lock_guard<std::mutex> lk(p.mu);
-    if (p.free.size() >= 64) {
-        (void)hipStreamDestroy(s);
-        return;
-    }
-    p.free.emplace_back(dev, s);
-}
-
-#define HIPCHK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) return fail(MR_ERR_DEVICE, std::string(#x ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T>
-static int upload(T *&dptr, const std::vector<T> &h) {
-    dptr = nullptr;
-    size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-    HIPCHK(pmalloc(reinterpret_cast<void **>(&dptr), bytes));
-    if (!h.empty()) HIPCHK(hipMemcpy(dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return MR_OK;
 }
 
 }  // namespace
@@ -1664,17 +1483,17 @@ static hipError_t copy_d2h(const D2HSeg *seg, int n, hipStream_t s) {
         for (size_t o = 0; o < seg[i].bytes; o += kChunk)
             ch.push_back({static_cast<char *>(seg[i].dst) + o, static_cast<const char *>(seg[i].src) + o,
                           std::min(kChunk, seg[i].bytes - o)});
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (hipEvent_t &x : ev)
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&x, hipEventDisableTiming);
+    Event ev[2];
+    for (Event &x : ev)
+        if (e == hipSuccess) e = x.create(hipEventDisableTiming);
     auto issue = [&](size_t c) {
         if (e == hipSuccess) e = hipMemcpyAsync(buf + (c % 2) * kChunk, ch[c].src, ch[c].bytes, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(ev[c % 2], s);
+        if (e == hipSuccess) e = hipEventRecord(ev[c % 2].get(), s);
     };
     for (size_t c = 0; c < ch.size() && c < 2; ++c) issue(c);
     HostPool &pool = HostPool::get();
     for (size_t c = 0; c < ch.size() && e == hipSuccess; ++c) {
-        e = hipEventSynchronize(ev[c % 2]);
+        e = hipEventSynchronize(ev[c % 2].get());
         if (e != hipSuccess) break;
         const char *from = buf + (c % 2) * kChunk;
         const uint32_t parts = ch[c].bytes >= (size_t(1) << 20) ? pool.size() : 1u;
@@ -1685,18 +1504,6 @@ static hipError_t copy_d2h(const D2HSeg *seg, int n, hipStream_t s) {
         if (c + 2 < ch.size()) issue(c + 2);
     }
     (void)hipStreamSynchronize(s);  // nothing may still write the stage once it is unlocked
-    for (hipEvent_t x : ev)
-        if (x) (void)hipEventDestroy(x);
-    return e;
-}
-
-static hipError_t dev_malloc(void **p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        trim_cache_all();
-        e = hipMalloc(p, bytes);
-    }
     return e;
 }
 
@@ -1711,23 +1518,20 @@ extern "C" int mr_grid_region_table(mr_grid *g, uint32_t homeland, uint32_t *out
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return fail(MR_ERR_DEVICE, "hipGetDevice");
     const uint32_t *rank = grid_rank_device(g, dev);
-    uint32_t *own = nullptr;
+    DevBuf<uint32_t> own;
     if (!rank) {  // the grid's tables live on another device: this one gets its own rank copy
-        if (dev_malloc(reinterpret_cast<void **>(&own), size_t(g->V) * 4) != hipSuccess ||
-            hipMemcpy(own, g->rank.data(), size_t(g->V) * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            if (own) (void)hipFree(own);
-            return fail(MR_ERR_DEVICE, "rank table upload");
-        }
-        rank = own;
+        if (upload(own, g->rank, DevMem::direct) != hipSuccess) return fail(MR_ERR_DEVICE, "rank table upload");
+        rank = own.get();
     }
     const uint32_t *d = region_table_device(g, int(homeland), rank);
-    if (own) (void)hipFree(own);
     if (!d) return fail(MR_ERR_DEVICE, "region table build");
     if (build_ms) *build_ms = g->region_ms[homeland];
     if (out && words && hipMemcpy(out, d, words * 4, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(MR_ERR_DEVICE, "region table copy");
     return MR_OK;
 }
+
+extern "C" void mr_cache_live(uint64_t *blocks, uint64_t *bytes) { cache_live(blocks, bytes); }
 
 extern "C" void mr_cache_trim(void) {
     trim_cache_all();
@@ -1757,56 +1561,38 @@ extern "C" int mr_host_unregister(void *p) {
     return MR_OK;
 }
 
+// A plan's members own what they name: a DevBuf returns its block to the cache, a Stream
+// goes back to the pool, an Event is destroyed, each when the plan is (mr_plan_destroy
+// waits for the plan's passes first).  Streams and events are declared before the buffers,
+// so they go last.
 struct mr_plan {
     const mr_grid *grid = nullptr;
     HostPlan hp;
-    KArgs ka{};
-    bool grid_in_lds = false;
-    uint32_t blocks = 0;
-    uint32_t *d_sinfo = nullptr, *d_rank = nullptr, *d_rank_inv = nullptr, *d_src = nullptr, *d_qb = nullptr,
-             *d_qd = nullptr, *d_qi = nullptr;
-    KArgs *d_args = nullptr;
-    KArgs *d_args_fb = nullptr;           // SSSP launch over the hub solver's fallback list
-    KArgs *d_args_hub_last = nullptr;     // hub launch that ends the pass (fallback known to be empty)
-    KArgs *d_args_lane = nullptr;         // hub_lane_kernel launch (sources [0, n_lane))
-    KArgs *d_args_lane_last = nullptr;    // the same, ending the pass
-    uint32_t n_lane = 0;                  // sources on the lane kernel; the rest on hub_kernel
-    uint32_t lane_g = 0;                  // > 0: the n_lane sources run G lanes each (hub_group_kernel)
-    KArgs *d_args_fill = nullptr;         // all-destinations mode: the fill launch (ends the pass)
+    KArgs ka{};  // all but the per-pass fields, which slot_args() fills from a slot
+    int device = 0;
     bool all_mode = false;
-    CellWord *d_rec = nullptr;            // all-destinations outputs (KArgs::out_rec ...)
-    Rec *d_tab = nullptr;
-    uint32_t *d_lex = nullptr, *d_sstate = nullptr;
+    bool grid_in_lds = false;
+    uint32_t algo = kAlgoGeneric;
+    uint32_t blocks = 0, cus = 256;
     std::vector<uint32_t> src_of_input;   // caller's source i -> plan source index
     bool fb_none = false;                 // a completed pass of this plan had no fallback sources
     uint32_t runs = 0;
     double fill_ms = 0.0;                 // all-destinations: average fill launch of the last window
-    uint32_t *d_near = nullptr, *d_fb = nullptr;
-    uint32_t *d_near_sp = nullptr, *d_rb_off = nullptr, *d_rb_cell = nullptr;  // wide hub tables
-    uint32_t *d_lane_blob = nullptr;  // lane / group kernels: the plan's LDS block (lane_blob_build)
-    std::shared_ptr<mr_grid::LaneMemo> memo;  // lane memo rows (the grid's; ka.lane_memo when the gate holds)
-    uint32_t *d_relist = nullptr;     // lane kernel (Fleetfoot): uncertain sources for hub_kernel (KArgs::relist)
-    OutCmd *d_ovf = nullptr;              // command-overflow pool (labels longer than max_cmds)
-    // outputs bound with an overflow buffer (a collective gathers them raw): each pass
-    // ends with ovf_order_kernel, which puts the pool in record order (d_ovf_tmp: its staging)
-    OutCmd *d_ovf_tmp = nullptr;
-    bool ovf_order = false;
-    uint32_t hub_blocks = 0, fb_blocks = 0, spw = 1, cus = 256, fill_per_cu = 8;
-    unsigned long long *d_dbg = nullptr;  // diagnostic builds: per-workgroup phase cycles
-    uint32_t algo = kAlgoGeneric;
-    SpecialStatic *d_sp = nullptr;
-    uint16_t *d_hubs = nullptr;
-    OutResult *d_res = nullptr;
-    OutCmd *d_cmd = nullptr;
-    uint32_t *d_ws = nullptr, *d_counter = nullptr;
-    hipStream_t stream = nullptr;
+
+    Stream stream;      // the plan's own
+    Stream hub_stream;  // overlap on two streams: the specials' solves of every slot
     hipStream_t last_stream = nullptr;    // the stream the latest pass ran on
-    hipEvent_t ev_last = nullptr;         // the end event of the latest pass (on the caller's stream)
-    bool ev_last_orphan = false;          // ev_last was folded out of `timed` and is owned here
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;  // pending event pairs
-    // whole: the pass is the fill launch (the pass pair times it)
+    hipEvent_t ev_last = nullptr;         // the end event of the latest pass (on the caller's stream): a view
+    Event ev_last_keep;                   // owns ev_last once its pair was folded out of `timed` (or it never had one)
+    struct TimedPass {
+        Event first, second;
+    };
+    std::vector<TimedPass> timed;  // pending event pairs
+    // second: the pass's end event (owned by `timed`); whole: the pass is the fill launch
+    // (the pass pair times it)
     struct FillTimed {
-        hipEvent_t first, second;
+        Event first;
+        hipEvent_t second;
         bool whole;
     };
     std::vector<FillTimed> timed_fill;  // all-destinations: fill launches
@@ -1814,188 +1600,169 @@ struct mr_plan {
     // must not pile up events: mr_plan_run folds the oldest beyond kMaxTimed)
     double acc_ms = 0.0, acc_fill_ms = 0.0;
     uint32_t acc_n = 0, acc_fill_n = 0;
-    int device = 0;
-    // All-destinations plans run the specials' solves of the next passes (hub kernels,
-    // in order on the plan's hub stream) beside the fill of pass k (on the caller's
-    // stream).  The per-pass buffers and kernel arguments come in slots taken round
-    // robin; the d_* fields above always name the slot of the latest pass (use_slot).
-    // One hub stream for every slot: more streams than the process's hardware queues
-    // (GPU_MAX_HW_QUEUES, 4) alias, and a hub queued behind a fill serialises the two.
+
+    // the map's tables: views of the grid's shared copies, or of the plan's own where the
+    // grid's live on another device; the special table and the caravan hubs
+    struct Tables {
+        DevBuf<uint32_t> own_sinfo, own_rank, own_rank_inv;
+        DevBuf<uint2> own_cell;
+        uint32_t *sinfo = nullptr, *rank = nullptr, *rank_inv = nullptr;
+        uint2 *cell = nullptr;
+        DevBuf<SpecialStatic> sp;
+        DevBuf<uint16_t> hubs;
+    } tab;
+    // the per-batch arrays in one block (src, qb, qd, qi point into it)
+    struct Batch {
+        DevBuf<uint32_t> block;
+        uint32_t *src = nullptr, *qb = nullptr, *qd = nullptr, *qi = nullptr;
+        DevBuf<char> gscratch;   // device grouping: phase 1's scratch, until the partition (plan_partition)
+        DevBuf<uint32_t> gcnt;   // device grouping: its counts
+        void take(DevBuf<uint32_t> &&b, const size_t at[4]) {
+            block = std::move(b);
+            src = block.get() + at[0], qb = block.get() + at[1], qd = block.get() + at[2], qi = block.get() + at[3];
+        }
+    } batch;
+    struct Outputs {
+        DevBuf<OutResult> res;
+        DevBuf<OutCmd> cmd;
+        DevBuf<OutCmd> ovf;                // command-overflow pool (labels longer than max_cmds)
+        // outputs bound with an overflow buffer (a collective gathers them raw): each pass
+        // ends with ovf_order_kernel, which puts the pool in record order (ovf_tmp: its staging)
+        DevBuf<OutCmd> ovf_tmp;
+        bool ovf_order = false;
+        DevBuf<CellWord> rec;              // all-destinations records (KArgs::out_rec)
+        DevBuf<uint32_t> ws;               // the SSSP kernel's HBM slots
+        DevBuf<unsigned long long> dbg;    // diagnostic builds: per-workgroup phase cycles
+    } out;
+    struct Hub {
+        uint32_t n_lane = 0;               // sources on the lane kernel; the rest on hub_kernel
+        uint32_t lane_g = 0;               // > 0: the n_lane sources run G lanes each (hub_group_kernel)
+        uint32_t hub_blocks = 0, fb_blocks = 0, spw = 1, fill_per_cu = 8;
+        DevBuf<KArgs> args_hub_last;       // hub launch that ends the pass (fallback known to be empty)
+        DevBuf<KArgs> args_lane;           // hub_lane_kernel launch (sources [0, n_lane))
+        DevBuf<KArgs> args_lane_last;      // the same, ending the pass
+        DevBuf<uint32_t> near_sp, rb_off, rb_cell;  // wide hub tables
+        DevBuf<uint32_t> relist;           // lane kernel (Fleetfoot): uncertain sources for hub_kernel (KArgs::relist)
+        DevBuf<uint32_t> lane_blob;        // lane / group kernels: the plan's LDS block (lane_blob_build)
+        std::shared_ptr<mr_grid::LaneMemo> memo;  // lane memo rows (the grid's; ka.lane_memo when the gate holds)
+    } hub;
+    // certified fallback (query hub plans, DESIGN.md section 3d): per slot a label table,
+    // boundary ranks, source, cell words, check state and sweep list; the fill's
+    // argument block over the slots
+    struct Cert {
+        uint32_t cap = 0, fill_gx = 1, check_gx = 1, tile_wgs = 0;
+        DevBuf<Rec> tab, stage_tab;
+        DevBuf<uint32_t> lex, src, st, aux, fb, ones, stage_lex, stage_src;
+        DevBuf<CellWord> rec;
+        DevBuf<uint32_t> win;              // per slot the repair window (cert_window_kernel)
+        DevBuf<unsigned long long> pub;    // the tile sweep's publish areas
+        DevBuf<uint32_t> redo;             // per slot: redone in the second round (cert_promote_kernel)
+        DevBuf<KArgs> args, args_r2, args_cert_r2;  // the closed forms' fill; the second round's blocks
+    } cert;
+    // What a pass writes before its records and the argument blocks that name it.  Every
+    // plan has one; all-destinations plans that run the specials' solves of the next
+    // passes (hub kernels, in order on the hub stream, or the first workgroups of the fused
+    // launch) beside the fill of pass k take them round robin.  One hub stream for every
+    // slot: more streams than the process's hardware queues (GPU_MAX_HW_QUEUES, 4) alias,
+    // and a hub queued behind a fill serialises the two.
     struct Slot {
-        Rec *tab = nullptr;
-        uint32_t *lex = nullptr, *sstate = nullptr, *fb = nullptr, *counter = nullptr;
-        KArgs *args = nullptr, *args_fb = nullptr, *args_fill = nullptr;
-        hipEvent_t ev_hub = nullptr, ev_fill = nullptr;
+        DevBuf<Rec> tab;
+        DevBuf<uint32_t> lex, sstate, fb, counter;
+        DevBuf<KArgs> args;
+        DevBuf<KArgs> args_fb;    // SSSP launch over the hub solver's fallback list
+        DevBuf<KArgs> args_fill;  // all-destinations mode: the fill launch (ends the pass)
+        Event ev_hub, ev_fill;
         bool used = false;    // a pass has run in this slot
         bool solved = false;  // fused: a launch has solved the specials of this slot's next pass
     };
-    std::vector<Slot> slots;  // slot 0 holds the plan's first buffers; empty: no overlap
-    hipStream_t hub_stream = nullptr;
-    bool overlap = false;
+    std::vector<Slot> slots = std::vector<Slot>(1);
+    uint32_t slot = 0;     // the slot of the latest pass
+    bool overlap = false;  // more than one slot
     // overlap in one launch per pass (hub_fill_kernel): the specials of pass k + 1 are
     // solved by the first workgroups of pass k's fill launch (MR_FILL_FUSED=0: the two
     // streams instead)
     bool fused = false;
     uint32_t hub_lds = 0, fused_per_cu = 0;
-    uint32_t slot = 0;     // slot index of the d_* fields
-    bool own_tables = true;  // d_sinfo / d_rank / d_rank_inv / d_cell: false = the grid's shared copies
-    uint2 *d_cell = nullptr;
-    uint32_t *d_qblock = nullptr;  // the per-batch arrays (d_src, d_qb, d_qd, d_qi point into it)
-    void *d_gscratch = nullptr;    // device grouping: phase 1's scratch, until the partition (plan_create)
-    uint32_t *d_gcnt = nullptr;    // device grouping: its counts
-    // certified fallback (query hub plans, DESIGN.md section 3d): per slot a label table,
-    // boundary ranks, source, cell words, check state and sweep list; the fill's
-    // argument block over the slots
-    uint32_t cert_cap = 0, cert_fill_gx = 1, cert_check_gx = 1, cert_tile_wgs = 0;
-    Rec *d_cert_tab = nullptr;
-    uint32_t *d_cert_win = nullptr;               // per slot the repair window (cert_window_kernel)
-    uint32_t *d_cert_redo = nullptr;              // per slot: redone in the second round (cert_promote_kernel)
-    KArgs *d_args_r2 = nullptr, *d_args_cert_r2 = nullptr;  // the second round's argument blocks
-    unsigned long long *d_cert_pub = nullptr;     // the tile sweep's publish areas
-    uint32_t *d_cert_lex = nullptr, *d_cert_src = nullptr, *d_cert_st = nullptr, *d_cert_aux = nullptr,
-             *d_fb_cert = nullptr, *d_cert_ones = nullptr;
-    CellWord *d_cert_rec = nullptr;
-    KArgs *d_args_cert = nullptr;
-    Rec *d_cert_stage_tab = nullptr;
-    uint32_t *d_cert_stage_lex = nullptr, *d_cert_stage_src = nullptr;
-    ~mr_plan() {
-        if (!slots.empty()) {  // the d_* fields may name another slot: free each slot's once
-            Slot &k = slots[0];
-            d_tab = k.tab;
-            d_lex = k.lex;
-            d_sstate = k.sstate;
-            d_fb = k.fb;
-            d_counter = k.counter;
-            d_args = k.args;
-            d_args_fb = k.args_fb;
-            d_args_fill = k.args_fill;
-            k.tab = nullptr;
-            k.lex = k.sstate = k.fb = k.counter = nullptr;
-            k.args = k.args_fb = k.args_fill = nullptr;
-        }
-        for (Slot &k : slots) {
-            for (void *p : {(void *)k.tab, (void *)k.lex, (void *)k.sstate, (void *)k.fb, (void *)k.counter,
-                            (void *)k.args, (void *)k.args_fb, (void *)k.args_fill})
-                if (p) (void)pfree(p);
-            for (hipEvent_t e : {k.ev_hub, k.ev_fill})
-                if (e) (void)hipEventDestroy(e);
-        }
-        pstream_release(hub_stream);
-        d_src = d_qb = d_qd = d_qi = nullptr;  // inside d_qblock
-        pfree(d_qblock);
-        pfree(d_gscratch);
-        pfree(d_gcnt);
-        if (!own_tables) {  // the grid's
-            d_sinfo = d_rank = d_rank_inv = nullptr;
-            d_cell = nullptr;
-        }
-        if (d_cell) (void)pfree(d_cell);
-        for (void *p : {(void *)d_cert_tab, (void *)d_cert_lex, (void *)d_cert_src, (void *)d_cert_st,
-                        (void *)d_cert_aux, (void *)d_fb_cert, (void *)d_cert_ones, (void *)d_cert_rec,
-                        (void *)d_args_cert, (void *)d_cert_stage_tab, (void *)d_cert_stage_lex,
-                        (void *)d_cert_stage_src, (void *)d_cert_win, (void *)d_cert_pub, (void *)d_cert_redo,
-                        (void *)d_args_r2, (void *)d_args_cert_r2})
-            if (p) (void)pfree(p);
-        for (void *p : {(void *)d_sinfo, (void *)d_rank, (void *)d_rank_inv, (void *)d_src, (void *)d_qb, (void *)d_qd,
-                        (void *)d_qi, (void *)d_sp, (void *)d_hubs, (void *)d_res, (void *)d_cmd, (void *)d_ws,
-                        (void *)d_counter, (void *)d_args, (void *)d_dbg, (void *)d_args_fb, (void *)d_near,
-                        (void *)d_fb, (void *)d_args_hub_last, (void *)d_args_fill, (void *)d_rec,
-                        (void *)d_args_lane, (void *)d_args_lane_last, (void *)d_relist,
-                        (void *)d_tab,
-                        (void *)d_lex, (void *)d_sstate, (void *)d_near_sp, (void *)d_rb_off, (void *)d_rb_cell, (void *)d_ovf,
-                        (void *)d_lane_blob, (void *)d_ovf_tmp})
-            if (p) (void)pfree(p);
-        if (ev_last && ev_last_orphan) (void)hipEventDestroy(ev_last);
-        for (auto &e : timed) {
-            (void)hipEventDestroy(e.first);
-            (void)hipEventDestroy(e.second);
-        }
-        for (auto &f : timed_fill)  // its end event is the pass's, destroyed above
-            if (f.first) (void)hipEventDestroy(f.first);
-        pstream_release(stream);
-    }
+    Slot &cur() { return slots[slot]; }
+    uint32_t next_slot() const { return runs >= 1 ? (slot + 1) % uint32_t(slots.size()) : 0u; }
 };
 
-// all-destinations overlap: make slot i's buffers and argument blocks current
-static void use_slot(mr_plan *pl, uint32_t i) {
+// the kernel arguments of a pass in slot i
+static KArgs slot_args(const mr_plan *pl, uint32_t i) {
     const mr_plan::Slot &k = pl->slots[i];
-    pl->d_tab = k.tab;
-    pl->d_lex = k.lex;
-    pl->d_sstate = k.sstate;
-    pl->d_fb = k.fb;
-    pl->d_counter = k.counter;
-    pl->d_args = k.args;
-    pl->d_args_fb = k.args_fb;
-    pl->d_args_fill = k.args_fill;
-    pl->ka.out_tab = k.tab;
-    pl->ka.out_lex = k.lex;
-    pl->ka.src_state = k.sstate;
-    pl->ka.fb_list = k.fb;
-    pl->ka.counter = k.counter;
-    pl->slot = i;
+    KArgs a = pl->ka;
+    a.out_tab = k.tab.get();
+    a.out_lex = k.lex.get();
+    a.src_state = k.sstate.get();
+    a.fb_list = k.fb.get();
+    a.counter = k.counter.get();
+    return a;
 }
 
-// Kernel-argument blocks of a plan: the main launch, and for hub plans the fallback
+// Kernel-argument blocks of slot i: the main launch, and for hub plans the fallback
 // launch and the hub launch that ends a pass on its own (last_launch marks the
 // kernel whose last workgroup resets the per-pass counters).
-static int upload_args(mr_plan *pl) {
+static int upload_args(mr_plan *pl, uint32_t i = 0) {
     // every block queued on the plan's stream, then one synchronisation (a blocking copy
     // each cost ~10 us: up to six per plan); the host copies live in `held` until then.
     // Callers hold a drained plan, so nothing of the stream's is in flight.
     KArgs held[8];
     uint32_t nh = 0;
     bool ok = true;
-    auto put = [&](KArgs *d, const KArgs &k) {
+    const hipStream_t s = pl->stream.get();
+    auto put = [&](const DevBuf<KArgs> &d, const KArgs &k) {
         held[nh] = k;
-        ok = ok && hipMemcpyAsync(d, &held[nh], sizeof(KArgs), hipMemcpyHostToDevice, pl->stream) == hipSuccess;
+        ok = ok && hipMemcpyAsync(d.get(), &held[nh], sizeof(KArgs), hipMemcpyHostToDevice, s) == hipSuccess;
         ++nh;
         return ok;
     };
     struct Drain {
-        mr_plan *pl;
-        ~Drain() { (void)hipStreamSynchronize(pl->stream); }
-    } drain{pl};
-    KArgs k = pl->ka;
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{s};
+    const mr_plan::Slot &sl = pl->slots[i];
+    const mr_plan::Cert &ce = pl->cert;
+    KArgs k = slot_args(pl, i);
     const bool hub = pl->hp.hub;
     // tests: MR_DBG_INJECT_SLOT=<slot> makes the fill of that slot's passes raise a
     // device error flag (checks that errors of either overlap slot are reported)
     if (const char *e = std::getenv("MR_DBG_INJECT_SLOT"))
-        if (pl->all_mode && uint32_t(std::atoi(e)) == pl->slot) k.dbg_flags |= kDbgInjectFlag;
+        if (pl->all_mode && uint32_t(std::atoi(e)) == i) k.dbg_flags |= kDbgInjectFlag;
     // the pass ends with: the SSSP kernel (no hub), the fill kernel (all-destinations
     // hub plans), else the fallback launch or a lone hub launch
     k.last_launch = hub ? 0u : 1u;
-    if (!put(pl->d_args, k)) return MR_ERR_DEVICE;
+    if (!put(sl.args, k)) return MR_ERR_DEVICE;
     if (hub) {
         KArgs f = k;
         f.fb_mode = 1;
         f.last_launch = pl->all_mode ? 0u : 1u;
-        if (!put(pl->d_args_fb, f)) return MR_ERR_DEVICE;
+        if (!put(sl.args_fb, f)) return MR_ERR_DEVICE;
         KArgs l = k;
         l.last_launch = 1;
-        if (!put(pl->all_mode ? pl->d_args_fill : pl->d_args_hub_last, l)) return MR_ERR_DEVICE;
-        if (pl->d_args_cert) {  // the fill over the certificate slots the hub kernel exported
+        if (!put(pl->all_mode ? sl.args_fill : pl->hub.args_hub_last, l)) return MR_ERR_DEVICE;
+        if (ce.args) {  // the fill over the certificate slots the hub kernel exported
             KArgs c = k;
-            c.nsrc = pl->cert_cap;
-            c.nsrc_dev = pl->d_counter + kCtrCert;
-            c.src_v = pl->d_cert_src;
-            c.src_state = pl->d_cert_ones;
-            c.out_tab = pl->d_cert_tab;
-            c.out_lex = pl->d_cert_lex;
-            c.out_rec = pl->d_cert_rec;
-            if (!put(pl->d_args_cert, c)) return MR_ERR_DEVICE;
-            if (pl->d_args_r2) {  // the second round: only the slots cert_promote_kernel marked
+            c.nsrc = ce.cap;
+            c.nsrc_dev = sl.counter.get() + kCtrCert;
+            c.src_v = ce.src.get();
+            c.src_state = ce.ones.get();
+            c.out_tab = ce.tab.get();
+            c.out_lex = ce.lex.get();
+            c.out_rec = ce.rec.get();
+            if (!put(ce.args, c)) return MR_ERR_DEVICE;
+            if (ce.args_r2) {  // the second round: only the slots cert_promote_kernel marked
                 KArgs r = k;
-                r.cert_redo = pl->d_cert_redo;
-                c.src_state = pl->d_cert_redo;
-                if (!put(pl->d_args_r2, r) || !put(pl->d_args_cert_r2, c)) return MR_ERR_DEVICE;
+                r.cert_redo = ce.redo.get();
+                c.src_state = ce.redo.get();
+                if (!put(ce.args_r2, r) || !put(ce.args_cert_r2, c)) return MR_ERR_DEVICE;
             }
         }
         // (the lane kernel as the pass's only launch has no hub launch after it to relist into)
         KArgs ll = l;
         ll.relist = nullptr;
-        if (pl->d_args_lane && (!put(pl->d_args_lane, k) || !put(pl->d_args_lane_last, ll))) return MR_ERR_DEVICE;
+        if (pl->hub.args_lane && (!put(pl->hub.args_lane, k) || !put(pl->hub.args_lane_last, ll))) return MR_ERR_DEVICE;
     }
-    return ok && hipStreamSynchronize(pl->stream) == hipSuccess ? MR_OK : MR_ERR_DEVICE;
+    return ok && hipStreamSynchronize(s) == hipSuccess ? MR_OK : MR_ERR_DEVICE;
 }
 
 // The lane kernel adds metrics without overflow checks and keeps distances in 16
@@ -2081,26 +1848,23 @@ static std::shared_ptr<mr_grid::LaneMemo> lane_memo_rows(const mr_grid *g, int d
     }
     const uint32_t words = lane_memo_words(NS, nreg), rw = words / nrows;
     std::vector<uint32_t> rows(words);
-    uint32_t *d_src = nullptr;
-    KArgs *d_kb = nullptr;
+    DevBuf<uint32_t> d_src;
+    DevBuf<KArgs> d_kb;
     KArgs kb = ka;
-    bool ok = dev_malloc(reinterpret_cast<void **>(&m->d_rows), size_t(words) * 4) == hipSuccess &&
-              dev_malloc(reinterpret_cast<void **>(&d_src), size_t(nrows) * 4) == hipSuccess &&
-              dev_malloc(reinterpret_cast<void **>(&d_kb), sizeof(KArgs)) == hipSuccess;
+    bool ok = m->d_rows.alloc(words, DevMem::direct) == hipSuccess && d_src.alloc(nrows, DevMem::direct) == hipSuccess &&
+              d_kb.alloc(1, DevMem::direct) == hipSuccess;
     if (ok) {
-        kb.src_v = d_src;
+        kb.src_v = d_src.get();
         kb.n_lane = nrows;
-        kb.lane_memo = m->d_rows;
+        kb.lane_memo = m->d_rows.get();
         kb.relist = nullptr;
         kb.dbg = nullptr;
-        ok = hipMemcpy(d_src, srcs.data(), size_t(nrows) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(d_kb, &kb, sizeof(KArgs), hipMemcpyHostToDevice) == hipSuccess &&
-             launch_lane_memo_build(d_kb, hp.p.perm, NS, nreg, stream) == hipSuccess &&
+        ok = hipMemcpy(d_src.get(), srcs.data(), size_t(nrows) * 4, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(d_kb.get(), &kb, sizeof(KArgs), hipMemcpyHostToDevice) == hipSuccess &&
+             launch_lane_memo_build(d_kb.get(), hp.p.perm, NS, nreg, stream) == hipSuccess &&
              hipStreamSynchronize(stream) == hipSuccess &&
-             hipMemcpy(rows.data(), m->d_rows, size_t(words) * 4, hipMemcpyDeviceToHost) == hipSuccess;
+             hipMemcpy(rows.data(), m->d_rows.get(), size_t(words) * 4, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    if (d_src) (void)hipFree(d_src);
-    if (d_kb) (void)hipFree(d_kb);
     if (!ok) {
         (void)hipGetLastError();
         return nullptr;
@@ -2223,62 +1987,59 @@ static int group_on_device(mr_plan *pl, const mr_query *qs, uint32_t n) {
     geo.V = g->V;
     size_t at[5];
     qblock_layout(n, at);
-    void *d_q = nullptr;
+    // (d_q goes back to the cache on return, after the syncs below: the cache hands blocks
+    // out without one)
+    DevBuf<char> d_qbuf;
+    DevBuf<uint32_t> blk;
+    mr_plan::Batch &ba = pl->batch;
     const size_t qbytes = size_t(n) * sizeof(mr_query);
-    if (pmalloc(reinterpret_cast<void **>(&pl->d_qblock), at[4] * 4) != hipSuccess ||
-        pmalloc(&d_q, qbytes) != hipSuccess || pmalloc(&pl->d_gscratch, group_scratch_bytes(n, g->V)) != hipSuccess ||
-        pmalloc(reinterpret_cast<void **>(&pl->d_gcnt), 8 * 4 + 4096 * 4) != hipSuccess) {
-        pfree(d_q);
+    if (blk.alloc(at[4]) != hipSuccess || d_qbuf.alloc(qbytes) != hipSuccess ||
+        ba.gscratch.alloc(group_scratch_bytes(n, g->V)) != hipSuccess || ba.gcnt.alloc(8 + 4096) != hipSuccess)
         return fail(MR_ERR_DEVICE, "hipMalloc device grouping");
-    }
-    pl->d_src = pl->d_qblock + at[0];
-    pl->d_qb = pl->d_qblock + at[1];
-    pl->d_qd = pl->d_qblock + at[2];
-    pl->d_qi = pl->d_qblock + at[3];
+    ba.take(std::move(blk), at);
+    void *const d_q = d_qbuf.get();
+    const hipStream_t ps = pl->stream.get();
     hipError_t e = hipSuccess;
     if (host_pinned(qs, qbytes)) {
-        e = hipMemcpyAsync(d_q, qs, qbytes, hipMemcpyHostToDevice, pl->stream);
+        e = hipMemcpyAsync(d_q, qs, qbytes, hipMemcpyHostToDevice, ps);
     } else {
         PinnedStage &su = stage_up();
         std::lock_guard<std::mutex> lk(su.mu);
         constexpr size_t kUp = size_t(4) << 20;
         char *stage = static_cast<char *>(su.get(std::min(qbytes, 2 * kUp)));
         if (!stage) {
-            e = hipMemcpyAsync(d_q, qs, qbytes, hipMemcpyHostToDevice, pl->stream);
+            e = hipMemcpyAsync(d_q, qs, qbytes, hipMemcpyHostToDevice, ps);
         } else {
             // two stage halves in turn: a half is refilled only after its previous DMA
-            hipEvent_t done[2] = {nullptr, nullptr};
-            for (hipEvent_t &ev : done)
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+            Event done[2];
+            for (Event &ev : done)
+                if (e == hipSuccess) e = ev.create(hipEventDisableTiming);
             HostPool &hpool = HostPool::get();
             const char *src = reinterpret_cast<const char *>(qs);
             uint32_t c = 0;
             for (size_t lo = 0; lo < qbytes && e == hipSuccess; lo += kUp, ++c) {
                 const size_t len = std::min(kUp, qbytes - lo);
                 char *half = stage + (c & 1u) * kUp;
-                if (c >= 2 && (e = hipEventSynchronize(done[c & 1u])) != hipSuccess) break;
+                if (c >= 2 && (e = hipEventSynchronize(done[c & 1u].get())) != hipSuccess) break;
                 const uint32_t parts = len >= (size_t(1) << 20) ? hpool.size() : 1u;
                 hpool.run(parts, [&](uint32_t pt) {
                     const size_t a = len * pt / parts, b = len * (pt + 1) / parts;
                     std::memcpy(half + a, src + lo + a, b - a);
                 });
-                e = hipMemcpyAsync(static_cast<char *>(d_q) + lo, half, len, hipMemcpyHostToDevice, pl->stream);
-                if (e == hipSuccess) e = hipEventRecord(done[c & 1u], pl->stream);
+                e = hipMemcpyAsync(static_cast<char *>(d_q) + lo, half, len, hipMemcpyHostToDevice, ps);
+                if (e == hipSuccess) e = hipEventRecord(done[c & 1u].get(), ps);
             }
-            const hipError_t es = hipStreamSynchronize(pl->stream);  // (the stage is in use until here)
+            const hipError_t es = hipStreamSynchronize(ps);  // (the stage is in use until here)
             if (e == hipSuccess) e = es;
-            for (hipEvent_t ev : done)
-                if (ev) (void)hipEventDestroy(ev);
         }
     }
     uint32_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (e == hipSuccess)
-        e = group_queries_device(d_q, n, geo, kLaneMaxQ, pl->d_gscratch, pl->d_src, pl->d_qb, pl->d_qd, pl->d_qi,
-                                 pl->d_gcnt, pl->d_gcnt + 8, 4096, pl->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt, pl->d_gcnt, sizeof(cnt), hipMemcpyDeviceToHost, pl->stream);
-    const hipError_t es = hipStreamSynchronize(pl->stream);
+        e = group_queries_device(d_q, n, geo, kLaneMaxQ, ba.gscratch.get(), ba.src, ba.qb, ba.qd, ba.qi,
+                                 ba.gcnt.get(), ba.gcnt.get() + 8, 4096, ps);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt, ba.gcnt.get(), sizeof(cnt), hipMemcpyDeviceToHost, ps);
+    const hipError_t es = hipStreamSynchronize(ps);
     if (e == hipSuccess) e = es;
-    pfree(d_q);  // (after the sync: the cache hands blocks out without one)
     if (e != hipSuccess) return fail(MR_ERR_DEVICE, std::string("device grouping: ") + hipGetErrorString(e));
     hp.nrec = cnt[0];
     hp.nsrc = cnt[1];
@@ -2289,11 +2050,11 @@ static int group_on_device(mr_plan *pl, const mr_query *qs, uint32_t n) {
     if (ninv) {
         if (ninv <= 4096) {
             hp.invalid.resize(ninv);
-            if (hipMemcpy(hp.invalid.data(), pl->d_gcnt + 8, size_t(ninv) * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            if (hipMemcpy(hp.invalid.data(), ba.gcnt.get() + 8, size_t(ninv) * 4, hipMemcpyDeviceToHost) != hipSuccess)
                 return fail(MR_ERR_DEVICE, "device grouping: invalid list");
         } else {  // many invalid queries: every query not among the grouped ids
             std::vector<uint32_t> ids(cnt[0]);
-            if (cnt[0] && hipMemcpy(ids.data(), pl->d_qi, size_t(cnt[0]) * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            if (cnt[0] && hipMemcpy(ids.data(), ba.qi, size_t(cnt[0]) * 4, hipMemcpyDeviceToHost) != hipSuccess)
                 return fail(MR_ERR_DEVICE, "device grouping: query ids");
             std::vector<uint8_t> seen(n, 0);
             for (uint32_t i : ids) seen[i] = 1;
@@ -2311,23 +2072,18 @@ static uint32_t partition_on_device(mr_plan *pl) {
     if (hp.nsrc == 0) return 0;
     size_t at[5];
     qblock_layout(hp.nq, at);
-    uint32_t *blk = nullptr;
-    if (pmalloc(reinterpret_cast<void **>(&blk), at[4] * 4) != hipSuccess) return kNone32;
-    hipError_t e = partition_sources_device(hp.nq, pl->grid->V, hp.nsrc, kLaneMaxQ, lane_order_desc(), pl->d_gscratch, pl->d_src, pl->d_qb,
-                                            pl->d_qd, pl->d_qi, pl->d_gcnt, blk + at[0], blk + at[1], blk + at[2],
-                                            blk + at[3], pl->stream);
-    const hipError_t es = hipStreamSynchronize(pl->stream);
+    mr_plan::Batch &ba = pl->batch;
+    const hipStream_t ps = pl->stream.get();
+    DevBuf<uint32_t> blk;
+    if (blk.alloc(at[4]) != hipSuccess) return kNone32;
+    uint32_t *const b = blk.get();
+    hipError_t e = partition_sources_device(hp.nq, pl->grid->V, hp.nsrc, kLaneMaxQ, lane_order_desc(), ba.gscratch.get(),
+                                            ba.src, ba.qb, ba.qd, ba.qi, ba.gcnt.get(), b + at[0], b + at[1], b + at[2],
+                                            b + at[3], ps);
+    const hipError_t es = hipStreamSynchronize(ps);
     if (e == hipSuccess) e = es;
-    if (e != hipSuccess) {
-        pfree(blk);
-        return kNone32;
-    }
-    pfree(pl->d_qblock);
-    pl->d_qblock = blk;
-    pl->d_src = blk + at[0];
-    pl->d_qb = blk + at[1];
-    pl->d_qd = blk + at[2];
-    pl->d_qi = blk + at[3];
+    if (e != hipSuccess) return kNone32;
+    ba.take(std::move(blk), at);  // (the block it replaces goes back to the cache)
     return hp.n_small;
 }
 
@@ -2342,7 +2098,7 @@ static int host_arrays(const mr_plan *cpl) {
     hp.q_dst.assign(hp.nrec, 0u);
     hp.q_id.assign(hp.nrec, 0u);
     const std::pair<std::vector<uint32_t> *, const uint32_t *> arr[4] = {
-        {&hp.src_v, pl->d_src}, {&hp.q_begin, pl->d_qb}, {&hp.q_dst, pl->d_qd}, {&hp.q_id, pl->d_qi}};
+        {&hp.src_v, pl->batch.src}, {&hp.q_begin, pl->batch.qb}, {&hp.q_dst, pl->batch.qd}, {&hp.q_id, pl->batch.qi}};
     for (const auto &a : arr)
         if (!a.first->empty() &&
             hipMemcpy(a.first->data(), a.second, a.first->size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
@@ -2355,43 +2111,25 @@ static int host_arrays(const mr_plan *cpl) {
     return MR_OK;
 }
 
-static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *qs, uint32_t n, uint32_t max_cmds,
-                       mr_plan **out, bool all_mode = false) {
-    if (!out || (n && !qs)) return fail(MR_ERR_INVALID_ARG, "null argument");
-    *out = nullptr;
-    if (!mr_device_available()) return fail(MR_ERR_NO_DEVICE, "no gfx950 device visible (no CPU fallback)");
-    const double tm0 = timing_on() ? now_ms() : 0.0;
-    double tm_build = 0, tm_upload = 0, tm_alloc = 0;
-    auto pl = new mr_plan();
-    pl->grid = g;
-    int st = build_plan(g, prm, qs, n, max_cmds, pl->hp, !all_mode);
-    if (st == MR_OK && pl->hp.dev_grouped) {  // the batch grouped on the device (counts back)
-        if (hipGetDevice(&pl->device) != hipSuccess) st = fail(MR_ERR_DEVICE, "hipGetDevice");
-        else if (pstream_create(&pl->stream) != hipSuccess) st = fail(MR_ERR_DEVICE, "stream");
-        else st = group_on_device(pl, qs, n);
-    }
-    if (timing_on()) tm_build = now_ms();
-    if (st != MR_OK) {
-        delete pl;
-        return st;
-    }
-    HostPlan &hp = pl->hp;
-    // all destinations: hub_kernel + fill only, linear run times (the fill's keys)
-    if (all_mode && (hp.wide || hp.nonlin)) hp.hub = hp.wide = hp.nonlin = false;
-    // query plans with a linear run time and a table that fits a lane's registers: the
-    // sources with few queries run one per lane, when there are enough of them to give
-    // half of the SIMDs a wave (lane_min_sources); a lane-kernel wave runs a whole
-    // Dijkstra, so fewer waves than SIMDs leave it latency-bound and hub_kernel (a wave
-    // per source) is faster.  MR_HUB_LANE=0: never, =1: whenever applicable.
-    const char *hl = std::getenv("MR_HUB_LANE");
-    const bool lane_off = hl && !std::strcmp(hl, "0"), lane_force = hl && !std::strcmp(hl, "1");
-    // Plans the lane kernel does not take (too few sources to fill the GPU, or a table
-    // layout it does not hold) run one source per group of G lanes when the table fits 32
-    // entries: a source's Dijkstra is then ~G times shorter in wave instructions, which
-    // is what a small plan's pass time is (hub_group_kernel).  MR_HUB_GROUP=0: never,
-    // =8 / =16 / =32: the group size; MR_HUB_GROUP_FORCE=1: even where the lane
-    // kernel applies.  The certificate's table export is hub_kernel's, so
-    // MR_HUB_FALLBACK_ALL keeps hub_kernel.
+// ---- plan creation, step by step (plan_create runs them in this order: the block cache
+// hands out blocks in request order, and later steps read what earlier ones set) ----
+
+// Which kernel solves a hub plan's sources.
+// Query plans with a linear run time and a table that fits a lane's registers: the
+// sources with few queries run one per lane, when there are enough of them to give
+// half of the SIMDs a wave (lane_min_sources); a lane-kernel wave runs a whole
+// Dijkstra, so fewer waves than SIMDs leave it latency-bound and hub_kernel (a wave
+// per source) is faster.  MR_HUB_LANE=0: never, =1: whenever applicable.
+// Plans the lane kernel does not take (too few sources to fill the GPU, or a table
+// layout it does not hold) run one source per group of G lanes when the table fits 32
+// entries: a source's Dijkstra is then ~G times shorter in wave instructions, which
+// is what a small plan's pass time is (hub_group_kernel).  MR_HUB_GROUP=0: never,
+// =8 / =16 / =32: the group size; MR_HUB_GROUP_FORCE=1: even where the lane
+// kernel applies.  The certificate's table export is hub_kernel's, so
+// MR_HUB_FALLBACK_ALL keeps hub_kernel.
+enum class HubKernel { hub, lane, group8 = 8, group16 = 16, group32 = 32 };
+static HubKernel choose_kernel(const HostPlan &hp, bool all_mode) {
+    const bool lane_off = env_is("MR_HUB_LANE", "0"), lane_force = env_is("MR_HUB_LANE", "1");
     const char *hg = std::getenv("MR_HUB_GROUP");
     const uint32_t hgv = hg ? uint32_t(std::strtoul(hg, nullptr, 10)) : 8u;
     const bool group_off = hg && hgv == 0, group_force = std::getenv("MR_HUB_GROUP_FORCE") != nullptr;
@@ -2408,158 +2146,174 @@ static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *q
     // is relisted for a hub_kernel launch right after it, whose fallback reaches the
     // certificate (§3d) instead of the SSSP kernel.  MR_LANE_NONLIN=0: never; =1: the group
     // kernel for Time-first orders too.
-    const char *lnl = std::getenv("MR_LANE_NONLIN");
-    const bool lane_nl = hp.nonlin && hp.ff_magic_ok && !(lnl && !std::strcmp(lnl, "0"));
+    const bool lane_nl = hp.nonlin && hp.ff_magic_ok && !env_is("MR_LANE_NONLIN", "0");
     if (lane_ok && (!hp.nonlin || lane_nl) && !group_force && !lane_off && hub_lane_entries(hp.p.NS) != 0 &&
         lane_layout_ok(hp) && (lane_force || lane_sources(hp) >= lane_min_sources()))
-        pl->n_lane = hp.dev_grouped ? partition_on_device(pl) : partition_sources(hp);
+        return HubKernel::lane;
     // (the group kernel takes Fleetfoot plans that do not lead with Time: on Time-first
     // ones, c2-sized, hub_kernel's pass was 0.4-0.5 ms shorter, tools/r05/gpu_rates.sh)
-    else if (lane_ok && (!hp.nonlin || (lane_nl && (hp.p.perm[0] != 2u || (lnl && !std::strcmp(lnl, "1"))))) &&
-             !group_off && !lane_force && hub_group_slots(hp.p.NS, group_g) != 0 &&
-             !std::getenv("MR_HUB_FALLBACK_ALL")) {
-        pl->n_lane = nsrc_of(hp);
-        pl->lane_g = group_g;
+    if (lane_ok && (!hp.nonlin || (lane_nl && (hp.p.perm[0] != 2u || env_is("MR_LANE_NONLIN", "1")))) && !group_off &&
+        !lane_force && hub_group_slots(hp.p.NS, group_g) != 0 && !env_fallback_all())
+        return HubKernel(group_g);
+    return HubKernel::hub;
+}
+
+// the sources in the chosen kernel's order (the lane kernel: the small ones first)
+static int plan_partition(mr_plan *pl, HubKernel k) {
+    HostPlan &hp = pl->hp;
+    if (k == HubKernel::lane) {
+        pl->hub.n_lane = hp.dev_grouped ? partition_on_device(pl) : partition_sources(hp);
+    } else if (k != HubKernel::hub) {
+        pl->hub.n_lane = nsrc_of(hp);
+        pl->hub.lane_g = uint32_t(k);
     }
-    if (pl->d_gscratch) {  // phase 1's scratch is done with (the partition synchronised)
-        pfree(pl->d_gscratch);
-        pl->d_gscratch = nullptr;
-    }
-    auto bail = [&](int code) {
-        delete pl;
-        return code;
-    };
-    if (pl->n_lane == kNone32) return bail(fail(MR_ERR_DEVICE, "device partition of the sources"));
-    if (hipGetDevice(&pl->device) != hipSuccess) return bail(fail(MR_ERR_DEVICE, "hipGetDevice"));
-    if (grid_tables(g, pl->device, hp, pl->d_rank, pl->d_rank_inv, pl->d_sinfo, pl->d_cell)) {
-        pl->own_tables = false;
-    } else {
+    pl->batch.gscratch.reset();  // phase 1's scratch is done with (the partition synchronised)
+    if (pl->hub.n_lane == kNone32) return fail(MR_ERR_DEVICE, "device partition of the sources");
+    if (hipGetDevice(&pl->device) != hipSuccess) return fail(MR_ERR_DEVICE, "hipGetDevice");
+    return MR_OK;
+}
+
+// the grid's shared tables (or the plan's own copies), the special table and the hubs
+static int plan_tables(mr_plan *pl) {
+    const mr_grid *g = pl->grid;
+    const HostPlan &hp = pl->hp;
+    mr_plan::Tables &t = pl->tab;
+    hipError_t e = hipSuccess;
+    if (!grid_tables(g, pl->device, hp, t.rank, t.rank_inv, t.sinfo, t.cell)) {
         const std::vector<uint32_t> si = build_sinfo(g, hp);
-        if ((st = upload(pl->d_sinfo, si)) || (st = upload(pl->d_cell, build_cell(g, si))) ||
-            (st = upload(pl->d_rank, g->rank)) || (st = upload(pl->d_rank_inv, g->rank_inv)))
-            return bail(st);
+        e = upload(t.own_sinfo, si);
+        if (e == hipSuccess) e = upload(t.own_cell, build_cell(g, si));
+        if (e == hipSuccess) e = upload(t.own_rank, g->rank);
+        if (e == hipSuccess) e = upload(t.own_rank_inv, g->rank_inv);
+        t.sinfo = t.own_sinfo.get(), t.cell = t.own_cell.get(), t.rank = t.own_rank.get(), t.rank_inv = t.own_rank_inv.get();
     }
-    if ((st = upload(pl->d_sp, hp.sp)) || (st = upload(pl->d_hubs, hp.hubs)))
-        return bail(st);
-    if (!hp.dev_grouped) {  // the per-batch arrays in one device block and one copy (sources, offsets, destinations, query ids)
-        const size_t a0 = 0, a1 = a0 + (hp.src_v.size() + 63) / 64 * 64, a2 = a1 + (hp.q_begin.size() + 63) / 64 * 64,
-                     a3 = a2 + (hp.q_dst.size() + 63) / 64 * 64, a4 = a3 + (hp.q_id.size() + 63) / 64 * 64;
-        // packed in the pinned upload stage (host threads for large batches), one DMA
-        const size_t words = std::max<size_t>(a4, 1);
-        if (pmalloc(reinterpret_cast<void **>(&pl->d_qblock), words * 4) != hipSuccess)
-            return bail(fail(MR_ERR_DEVICE, "hipMalloc query block"));
-        {
-            PinnedStage &su = stage_up();
-            std::lock_guard<std::mutex> lk(su.mu);
-            uint32_t *pack = static_cast<uint32_t *>(su.get(words * 4));
-            std::vector<uint32_t> pv;
-            if (!pack) {
-                pv.assign(words, 0u);
-                pack = pv.data();
-            }
-            const std::vector<uint32_t> *arr[4] = {&hp.src_v, &hp.q_begin, &hp.q_dst, &hp.q_id};
-            const size_t at[4] = {a0, a1, a2, a3};
-            // words [a, b) of the block: the pieces of the four arrays that fall in them
-            auto pack_range = [&](size_t a, size_t b) {
-                for (int j = 0; j < 4; ++j) {
-                    const size_t s = std::max(a, at[j]), e = std::min(b, at[j] + arr[j]->size());
-                    if (s < e) std::memcpy(pack + s, arr[j]->data() + (s - at[j]), (e - s) * 4);
-                }
-            };
-            HostPool &hpool = HostPool::get();
-            if (words < (size_t(1) << 18)) {
-                pack_range(0, words);
-                if (hipMemcpy(pl->d_qblock, pack, words * 4, hipMemcpyHostToDevice) != hipSuccess)
-                    return bail(fail(MR_ERR_DEVICE, "upload query block"));
-            } else {
-                // 4 MB chunks: the DMA of chunk c runs while host threads pack chunk c + 1
-                // (packed and copied in one go: 0.85 ms at 1M queries)
-                constexpr size_t kUp = size_t(1) << 20;
-                const uint32_t parts = hpool.size();
-                hipError_t e = hipSuccess;
-                for (size_t lo = 0; lo < words && e == hipSuccess; lo += kUp) {
-                    const size_t hi = std::min(words, lo + kUp);
-                    hpool.run(parts, [&](uint32_t pt) {
-                        pack_range(lo + (hi - lo) * pt / parts, lo + (hi - lo) * (pt + 1) / parts);
-                    });
-                    e = hipMemcpyAsync(pl->d_qblock + lo, pack + lo, (hi - lo) * 4, hipMemcpyHostToDevice, nullptr);
-                }
-                // (the stage is not unlocked, nor the block used, before the copies are done)
-                const hipError_t es = hipStreamSynchronize(nullptr);
-                if (e != hipSuccess || es != hipSuccess) return bail(fail(MR_ERR_DEVICE, "upload query block"));
-            }
+    if (e == hipSuccess) e = upload(t.sp, hp.sp);
+    if (e == hipSuccess) e = upload(t.hubs, hp.hubs);
+    if (e != hipSuccess) return fail(MR_ERR_DEVICE, std::string("table upload: ") + hipGetErrorString(e));
+    return MR_OK;
+}
+
+// a host-grouped batch's arrays in one device block and one copy (sources, offsets,
+// destinations, query ids), packed in the pinned upload stage (host threads for large
+// batches), one DMA
+static int plan_batch_upload(mr_plan *pl) {
+    const HostPlan &hp = pl->hp;
+    if (hp.dev_grouped) return MR_OK;  // (group_on_device left them on the device)
+    const std::vector<uint32_t> *arr[4] = {&hp.src_v, &hp.q_begin, &hp.q_dst, &hp.q_id};
+    size_t at[5] = {0, 0, 0, 0, 0};
+    for (int j = 0; j < 4; ++j) at[j + 1] = at[j] + (arr[j]->size() + 63) / 64 * 64;
+    const size_t words = std::max<size_t>(at[4], 1);
+    DevBuf<uint32_t> blk;
+    if (blk.alloc(words) != hipSuccess) return fail(MR_ERR_DEVICE, "hipMalloc query block");
+    pl->batch.take(std::move(blk), at);
+    uint32_t *const d_blk = pl->batch.block.get();
+    PinnedStage &su = stage_up();
+    std::lock_guard<std::mutex> lk(su.mu);
+    uint32_t *pack = static_cast<uint32_t *>(su.get(words * 4));
+    std::vector<uint32_t> pv;
+    if (!pack) {
+        pv.assign(words, 0u);
+        pack = pv.data();
+    }
+    // words [a, b) of the block: the pieces of the four arrays that fall in them
+    auto pack_range = [&](size_t a, size_t b) {
+        for (int j = 0; j < 4; ++j) {
+            const size_t s = std::max(a, at[j]), e = std::min(b, at[j] + arr[j]->size());
+            if (s < e) std::memcpy(pack + s, arr[j]->data() + (s - at[j]), (e - s) * 4);
         }
-        pl->d_src = pl->d_qblock + a0;
-        pl->d_qb = pl->d_qblock + a1;
-        pl->d_qd = pl->d_qblock + a2;
-        pl->d_qi = pl->d_qblock + a3;
+    };
+    if (words < (size_t(1) << 18)) {
+        pack_range(0, words);
+        if (hipMemcpy(d_blk, pack, words * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(MR_ERR_DEVICE, "upload query block");
+        return MR_OK;
     }
-    if (timing_on()) tm_upload = now_ms();
-    size_t nres = std::max<uint32_t>(n, 1);
-    if (pmalloc(reinterpret_cast<void **>(&pl->d_res), nres * sizeof(OutResult)) != hipSuccess ||
-        pmalloc(reinterpret_cast<void **>(&pl->d_cmd), nres * size_t(max_cmds) * sizeof(OutCmd)) != hipSuccess ||
-        pmalloc(reinterpret_cast<void **>(&pl->d_ovf), std::max<size_t>(4096, size_t(n) * 8) * sizeof(OutCmd)) !=
-            hipSuccess ||
-        pmalloc(reinterpret_cast<void **>(&pl->d_counter), kCtrWords * 4) != hipSuccess ||
-        hipMemset(pl->d_counter, 0, kCtrWords * 4) != hipSuccess)
-        return bail(fail(MR_ERR_DEVICE, "hipMalloc outputs"));
+    // 4 MB chunks: the DMA of chunk c runs while host threads pack chunk c + 1
+    // (packed and copied in one go: 0.85 ms at 1M queries)
+    constexpr size_t kUp = size_t(1) << 20;
+    HostPool &hpool = HostPool::get();
+    const uint32_t parts = hpool.size();
+    hipError_t e = hipSuccess;
+    for (size_t lo = 0; lo < words && e == hipSuccess; lo += kUp) {
+        const size_t hi = std::min(words, lo + kUp);
+        hpool.run(parts, [&](uint32_t pt) {
+            pack_range(lo + (hi - lo) * pt / parts, lo + (hi - lo) * (pt + 1) / parts);
+        });
+        e = hipMemcpyAsync(d_blk + lo, pack + lo, (hi - lo) * 4, hipMemcpyHostToDevice, nullptr);
+    }
+    // (the stage is not unlocked, nor the block used, before the copies are done)
+    const hipError_t es = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess || es != hipSuccess) return fail(MR_ERR_DEVICE, "upload query block");
+    return MR_OK;
+}
+
+// min(want, resident) workgroups, at least one
+static uint32_t resident_grid(uint64_t want, uint64_t resident) {
+    return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(want, resident)));
+}
+// the fill's tiles of one source
+static uint64_t fill_tiles(uint32_t S) { return uint64_t((S + kFillTW - 1) / kFillTW) * ((S + kFillTH - 1) / kFillTH); }
+
+// the query outputs, the pass counters, and the SSSP kernel's algorithm, grid and workspace
+static int plan_outputs(mr_plan *pl, uint32_t n, uint32_t max_cmds) {
+    const HostPlan &hp = pl->hp;
+    const size_t nres = std::max<uint32_t>(n, 1);
+    if (pl->out.res.alloc(nres) != hipSuccess || pl->out.cmd.alloc(nres * size_t(max_cmds)) != hipSuccess ||
+        pl->out.ovf.alloc(std::max<size_t>(4096, size_t(n) * 8)) != hipSuccess ||
+        pl->slots[0].counter.alloc_zero(kCtrWords) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "hipMalloc outputs");
     // algorithm: level-synchronous when the comparator leads with Legs (MR_ALGO=generic forces the
     // bucketed solver, used by the tests to cover both); grid state in LDS when it fits 3
     // workgroups per CU, else per-workgroup HBM slots (MR_GRID_STATE=hbm|lds overrides)
     const uint32_t NS = hp.p.NS, V = hp.p.V;
     const uint32_t nsrc = nsrc_of(hp);
-    pl->algo = hp.p.bucket_mode == kBucketLegs ? kAlgoLegs : kAlgoGeneric;
-    if (const char *e = std::getenv("MR_ALGO"))
-        if (!std::strcmp(e, "generic")) pl->algo = kAlgoGeneric;
+    pl->algo = hp.p.bucket_mode == kBucketLegs && env_algo() != AlgoEnv::generic ? kAlgoLegs : kAlgoGeneric;
     const uint32_t lds_full = lds_bytes(NS, V, true, pl->algo);
     pl->grid_in_lds = V <= 65535 && lds_full <= 53 * 1024;
-    if (const char *e = std::getenv("MR_GRID_STATE")) {
-        if (!std::strcmp(e, "hbm")) pl->grid_in_lds = false;
-        else if (!std::strcmp(e, "lds") && V <= 65535 && lds_full <= 160 * 1024) pl->grid_in_lds = true;
-    }
-    uint32_t bytes = lds_bytes(NS, V, pl->grid_in_lds, pl->algo);
-    if (bytes > 160 * 1024) return bail(fail(MR_ERR_LIMIT, "special table exceeds LDS"));
-    const hipDeviceProp_t *propp = device_props(pl->device);
-    if (!propp) return bail(fail(MR_ERR_DEVICE, "props"));
-    const hipDeviceProp_t &prop = *propp;
-    pl->cus = uint32_t(prop.multiProcessorCount);
-    int per_cu = std::max(1, max_blocks_per_cu(pl->grid_in_lds, pl->algo, bytes));
-    uint64_t resident = uint64_t(per_cu) * uint64_t(prop.multiProcessorCount);
-    uint64_t blocks = std::min<uint64_t>(std::max<uint32_t>(nsrc, 1), resident);
-    if (hp.hub) blocks = std::min<uint64_t>(blocks, 2ull * prop.multiProcessorCount);  // fallback launches only
+    if (env_is("MR_GRID_STATE", "hbm")) pl->grid_in_lds = false;
+    else if (env_is("MR_GRID_STATE", "lds") && V <= 65535 && lds_full <= 160 * 1024) pl->grid_in_lds = true;
+    const uint32_t bytes = lds_bytes(NS, V, pl->grid_in_lds, pl->algo);
+    if (bytes > 160 * 1024) return fail(MR_ERR_LIMIT, "special table exceeds LDS");
+    const hipDeviceProp_t *prop = device_props(pl->device);
+    if (!prop) return fail(MR_ERR_DEVICE, "props");
+    pl->cus = uint32_t(prop->multiProcessorCount);
+    const int per_cu = std::max(1, max_blocks_per_cu(pl->grid_in_lds, pl->algo, bytes));
+    uint64_t blocks = std::min<uint64_t>(std::max<uint32_t>(nsrc, 1), uint64_t(per_cu) * pl->cus);
+    if (hp.hub) blocks = std::min<uint64_t>(blocks, 2ull * pl->cus);  // fallback launches only
     if (!pl->grid_in_lds) {
-        const uint64_t slot_bytes = 5ull * V * 4ull;
+        const uint64_t slot_words = 5ull * V;
         // HBM budget for solve slots; hub plans only solve the (few) fallback sources
         // (a hub plan's slots serve the few sources its closed form cannot certify: 2 GB
         // is ~95 slots at 1025^2 and ~6 at 4097^2, each looping over the sources)
         const uint64_t budget = (hp.hub ? 2ull : 64ull) << 30;
-        blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, budget / slot_bytes));
-        if (pmalloc(reinterpret_cast<void **>(&pl->d_ws), blocks * slot_bytes) != hipSuccess)
-            return bail(fail(MR_ERR_DEVICE, "hipMalloc workspace"));
+        blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, budget / (slot_words * 4ull)));
+        if (pl->out.ws.alloc(blocks * slot_words) != hipSuccess) return fail(MR_ERR_DEVICE, "hipMalloc workspace");
     }
     pl->blocks = uint32_t(blocks);
-    if (timing_on()) tm_alloc = now_ms();
-    if (!pl->stream && pstream_create(&pl->stream) != hipSuccess)
-        return bail(fail(MR_ERR_DEVICE, "stream"));
+    return MR_OK;
+}
+
+// the arguments every launch of the plan shares
+static void plan_base_args(mr_plan *pl, uint32_t n) {
+    const HostPlan &hp = pl->hp;
     KArgs &ka = pl->ka;
     ka.p = hp.p;
-    ka.sinfo = pl->d_sinfo;
-    ka.rank = pl->d_rank;
-    ka.rank_inv = pl->d_rank_inv;
-    ka.cell = pl->d_cell;
-    ka.sp = pl->d_sp;
-    ka.hubs = pl->d_hubs;
-    ka.src_v = pl->d_src;
-    ka.q_begin = pl->d_qb;
-    ka.q_dst = pl->d_qd;
-    ka.q_id = pl->d_qi;
-    ka.out_res = pl->d_res;
-    ka.out_cmd = pl->d_cmd;
-    ka.ws = pl->d_ws;
-    ka.counter = pl->d_counter;
-    ka.ovf = pl->d_ovf;
+    ka.sinfo = pl->tab.sinfo;
+    ka.rank = pl->tab.rank;
+    ka.rank_inv = pl->tab.rank_inv;
+    ka.cell = pl->tab.cell;
+    ka.sp = pl->tab.sp.get();
+    ka.hubs = pl->tab.hubs.get();
+    ka.src_v = pl->batch.src;
+    ka.q_begin = pl->batch.qb;
+    ka.q_dst = pl->batch.qd;
+    ka.q_id = pl->batch.qi;
+    ka.out_res = pl->out.res.get();
+    ka.out_cmd = pl->out.cmd.get();
+    ka.ws = pl->out.ws.get();
+    ka.ovf = pl->out.ovf.get();
     ka.ovf_cap = uint32_t(std::min<size_t>(std::max<size_t>(4096, size_t(n) * 8), 0xFFFFFFFFu));
-    ka.nsrc = nsrc;
+    ka.nsrc = nsrc_of(hp);
     ka.early_exit_max = 64;
     ka.grid_in_lds = pl->grid_in_lds ? 1u : 0u;
     ka.algo = pl->algo;
@@ -2567,280 +2321,291 @@ static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *q
     ka.near = nullptr;
     ka.lane_memo = nullptr;
     ka.nreg = 0;
-    ka.fb_list = nullptr;
     ka.fb_mode = 0;
-    ka.fb_all = std::getenv("MR_HUB_FALLBACK_ALL") ? 1u : 0u;  // tests cover the fallback path
-    ka.n_lane = pl->n_lane;
-    ka.rank_std = g->rank_std ? 1u : 0u;
-    ka.src_off = pl->n_lane;
+    ka.fb_all = env_fallback_all() ? 1u : 0u;  // tests cover the fallback path
+    ka.n_lane = pl->hub.n_lane;
+    ka.rank_std = pl->grid->rank_std ? 1u : 0u;
+    ka.src_off = pl->hub.n_lane;
     if (const char *e = std::getenv("MR_DBG_FLAGS")) ka.dbg_flags = uint32_t(std::atoi(e));
-    pl->all_mode = all_mode;
-    if (all_mode) {  // per source: a record per cell, the label table, the boundary ranks
-        const size_t T = size_t(NS) + 1;
-        // rows padded to whole 128 B lines (rec_pitch; MR_REC_ALIGN=64 pads to whole
-        // 64-cell tile rows): the fill never stores part of a line
-        uint32_t align = 32;
-        if (const char *e = std::getenv("MR_REC_ALIGN"))
-            if (std::atoi(e) == 64) align = 64;
-        const uint32_t pitch = (hp.p.S + align - 1) / align * align;
-        ka.rec_pitch = pitch;
-        if (pmalloc(reinterpret_cast<void **>(&pl->d_rec),
-                      std::max<size_t>(nsrc, 1) * hp.p.S * pitch * sizeof(CellWord)) != hipSuccess ||
-            pmalloc(reinterpret_cast<void **>(&pl->d_tab), std::max<size_t>(nsrc, 1) * T * sizeof(Rec)) != hipSuccess ||
-            pmalloc(reinterpret_cast<void **>(&pl->d_lex), std::max<size_t>(nsrc, 1) * T * 4) != hipSuccess ||
-            pmalloc(reinterpret_cast<void **>(&pl->d_sstate), std::max<size_t>(nsrc, 1) * 4) != hipSuccess)
-            return bail(fail(MR_ERR_DEVICE, "hipMalloc all-destinations outputs"));
-        ka.all_mode = 1;
-        ka.out_rec = pl->d_rec;
-        ka.out_tab = pl->d_tab;
-        ka.out_lex = pl->d_lex;
-        ka.src_state = pl->d_sstate;
-        ka.early_exit_max = 0;  // every cell must settle
-        pl->src_of_input.assign(n, kNone32);
-        for (uint32_t si = 0; si < nsrc; ++si)
-            for (uint32_t k = hp.q_begin[si]; k < hp.q_begin[si + 1]; ++k) pl->src_of_input[hp.q_id[k]] = si;
-    }
-    if (hp.hub) {
-        if (pmalloc(reinterpret_cast<void **>(&pl->d_fb), std::max<size_t>(nsrc, 1) * 4) != hipSuccess)
-            return bail(fail(MR_ERR_DEVICE, "hub tables"));
-        if (hp.near) {
-            ka.near = region_table_device(g, prm->homeland, pl->d_rank);
-            if (!ka.near) return bail(fail(MR_ERR_DEVICE, "region table build"));
-            if ((st = special_rows_from_table(g, prm->homeland, ka.near, hp.nreg, hp.sp, hp.near_sp)) != MR_OK)
-                return bail(fail(st, "region table rows"));
-        }
-        if (hp.wide) {
-            std::vector<uint32_t> off(hp.rb_off->begin(), hp.rb_off->end());
-            if (off.empty()) off.push_back(0);
-            if (upload(pl->d_near_sp, hp.near_sp) != MR_OK || upload(pl->d_rb_off, off) != MR_OK ||
-                upload(pl->d_rb_cell, *hp.rb_cell) != MR_OK)
-                return bail(fail(MR_ERR_DEVICE, "wide hub tables"));
-            ka.near_sp = pl->d_near_sp;
-            ka.rb_off = pl->d_rb_off;
-            ka.rb_cell = pl->d_rb_cell;
-        }
-        ka.nreg = hp.nreg;
-        ka.fb_list = pl->d_fb;
-        // two sources per wave when the specials fit 32 lanes (MR_HUB_SPW=1 forces one);
-        // the wide kernel runs one source per wave
-        pl->spw = !hp.wide && NS + 1 <= 32 ? 2u : 1u;
-        if (const char *e = std::getenv("MR_HUB_SPW"))
-            if (std::atoi(e) == 1) pl->spw = 1;
-        const uint32_t hb = hp.wide ? hub_wide_lds_bytes(NS, hp.nreg) : hub_lds_bytes(NS, hp.nreg, pl->spw);
-        if (hb > 160 * 1024) return bail(fail(MR_ERR_LIMIT, "hub tables exceed LDS"));
-        const int hper = std::max(1, hp.wide ? hub_wide_blocks_per_cu(hp.p.perm, NS, hb)
-                                             : hub_blocks_per_cu(hp.p.perm, pl->spw, hp.nonlin, hb));
-        // (a lane kernel with Fleetfoot relists its uncertain sources for hub_kernel: room
-        // for a few hundred of them in one round)
-        const bool relist = pl->n_lane && hp.nonlin;
-        const uint64_t per_block = 4ull * pl->spw, hub_src = std::max<uint64_t>(nsrc - pl->n_lane, relist ? 512u : 0u);
-        pl->hub_blocks = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((hub_src + per_block - 1) / per_block,
-                                                                           uint64_t(hper) * prop.multiProcessorCount)));
-        if (const char *e = std::getenv("MR_HUB_BLOCKS")) pl->hub_blocks = uint32_t(std::max(1, std::atoi(e)));
-        pl->fb_blocks = pl->blocks;
-        pl->fill_per_cu = uint32_t(std::max(1, fill_blocks_per_cu(hp.p.perm)));
-        if (pmalloc(reinterpret_cast<void **>(&pl->d_args_fb), sizeof(KArgs)) != hipSuccess ||
-            pmalloc(reinterpret_cast<void **>(&pl->d_args_hub_last), sizeof(KArgs)) != hipSuccess ||
-            pmalloc(reinterpret_cast<void **>(&pl->d_args_fill), sizeof(KArgs)) != hipSuccess)
-            return bail(fail(MR_ERR_DEVICE, "kernel args"));
-        // Certified fallback for query plans on hub_kernel (MR_CERT=0: off; MR_CERT_SLOTS:
-        // slots per pass, default by grid size): a flagged source's table goes to a slot, the fill
-        // writes its closed form over every cell, the check and one repair sweep decide
-        // whether its labels need the SSSP kernel at all.
-        const char *ce = std::getenv("MR_CERT");
-        if (!all_mode && !hp.wide && !(ce && !std::strcmp(ce, "0"))) {
-            // slots: as many as 512 MB of cell words and sweep lists hold, 8 to 64 (1025^2:
-            // 60; 4097^2: 8).  A Time-first Fleetfoot 1 batch of 125k on c4's map hands
-            // over ~40 sources, and every one without a slot costs a whole SSSP solve.
-            const size_t T = size_t(NS) + 1;
-            const uint32_t pitch = (hp.p.S + 31) / 32 * 32;
-            const size_t slot_bytes = size_t(V) * 4 + size_t(hp.p.S) * pitch * 4 + T * (sizeof(Rec) + 4);
-            uint32_t cap = uint32_t(std::min<size_t>(64, std::max<size_t>(8, (size_t(512) << 20) / slot_bytes)));
-            if (const char *e = std::getenv("MR_CERT_SLOTS")) cap = uint32_t(std::min(64, std::max(1, std::atoi(e))));
-            std::vector<uint32_t> ones(cap, 1u);
-            // staging for every fallback entry up to kCertStageMax (mr_engine.hpp): a
-            // pass with more hands nothing to the certificate
-            const uint32_t stage = uint32_t(std::min<size_t>(kCertStageMax, std::max<size_t>(nsrc, 1)));
-            if (pmalloc(reinterpret_cast<void **>(&pl->d_cert_stage_tab), stage * T * sizeof(Rec)) != hipSuccess ||
-                pmalloc(reinterpret_cast<void **>(&pl->d_cert_stage_lex), stage * T * 4) != hipSuccess ||
-                pmalloc(reinterpret_cast<void **>(&pl->d_cert_stage_src), stage * 4) != hipSuccess ||
-                pmalloc(reinterpret_cast<void **>(&pl->d_cert_tab), cap * T * sizeof(Rec)) != hipSuccess ||
-                pmalloc(reinterpret_cast<void **>(&pl->d_cert_lex), cap * T * 4) != hipSuccess ||
-                pmalloc(reinterpret_cast<void **>(&pl->d_cert_src), cap * 4) != hipSuccess ||
+}
 
-                pmalloc(reinterpret_cast<void **>(&pl->d_cert_aux), size_t(cap) * V * 4) != hipSuccess ||
-                pmalloc(reinterpret_cast<void **>(&pl->d_cert_rec), size_t(cap) * hp.p.S * pitch * 4) != hipSuccess ||
-                pmalloc(reinterpret_cast<void **>(&pl->d_fb_cert), std::max<size_t>(nsrc, 1) * 4) != hipSuccess ||
-                pmalloc(reinterpret_cast<void **>(&pl->d_args_cert), sizeof(KArgs)) != hipSuccess ||
-                upload(pl->d_cert_ones, ones) != MR_OK)
-                return bail(fail(MR_ERR_DEVICE, "certificate slots"));
-            pl->cert_cap = cap;
-            ka.cert_cap = cap;
-            ka.cert_stage_cap = stage;
-            ka.cert_stage_tab = pl->d_cert_stage_tab;
-            ka.cert_stage_lex = pl->d_cert_stage_lex;
-            ka.cert_stage_src = pl->d_cert_stage_src;
-            ka.cert_tab = pl->d_cert_tab;
-            ka.cert_lex = pl->d_cert_lex;
-            ka.cert_src = pl->d_cert_src;
-            ka.cert_st = pl->d_cert_st;
-            ka.cert_aux = pl->d_cert_aux;
-            ka.cert_rec = pl->d_cert_rec;
-            ka.fb_cert = pl->d_fb_cert;
-            ka.rec_pitch = pitch;
-            const uint64_t tiles = uint64_t((hp.p.S + kFillTW - 1) / kFillTW) * ((hp.p.S + kFillTH - 1) / kFillTH);
-            // (a workgroup's four waves a tile each, for every slot: the fill spreads the slots
-            // over groups of waves, and workgroups past the slots in use exit.  One slot's
-            // worth of workgroups left a small grid's 8 slots to 3 workgroups, one after the
-            // other: 0.34 ms of Fleetfoot fill at 65^2)
-            pl->cert_fill_gx = uint32_t(std::max<uint64_t>(
-                1, std::min<uint64_t>((tiles + 3) / 4 * cap, uint64_t(pl->fill_per_cu) * prop.multiProcessorCount)));
-            pl->cert_check_gx = uint32_t(std::max<uint64_t>(
-                1, std::min<uint64_t>((uint64_t(V) + 4 * 256 - 1) / (4 * 256), 4ull * prop.multiProcessorCount)));
-            // the check's state: one partial per slot and check workgroup, reduced by its readers
-            if (pmalloc(reinterpret_cast<void **>(&pl->d_cert_st), size_t(cap) * pl->cert_check_gx * kCertSt * 4) !=
-                hipSuccess)
-                return bail(fail(MR_ERR_DEVICE, "certificate slots"));
-            ka.cert_st = pl->d_cert_st;
-            ka.cert_parts = pl->cert_check_gx;
-            // the repair: per slot its window; the tile sweep's persistent grid (one
-            // workgroup a CU, each with two publish areas).  MR_CERT_TILE=0: the round-5
-            // sweep for every slot (A/B)
-            static const bool no_tile = [] {
-                const char *e = std::getenv("MR_CERT_TILE");
-                return e && std::atoi(e) == 0;
-            }();
-            const int occ = no_tile ? 0 : cert_tile_occupancy();
-            pl->cert_tile_wgs = occ > 0 ? uint32_t(occ) * uint32_t(prop.multiProcessorCount) : 0u;
-            // (+ one word: cert_window_kernel's completion count, zero between launches)
-            if (pmalloc(reinterpret_cast<void **>(&pl->d_cert_win), (size_t(cap) * kWinWords + 1) * 4) != hipSuccess ||
-                hipMemset(pl->d_cert_win, 0, (size_t(cap) * kWinWords + 1) * 4) != hipSuccess ||
-                (pl->cert_tile_wgs && pmalloc(reinterpret_cast<void **>(&pl->d_cert_pub),
-                                              size_t(pl->cert_tile_wgs) * 2 * kTileT * kTileT * 8) != hipSuccess))
-                return bail(fail(MR_ERR_DEVICE, "certificate slots"));
-            ka.cert_win = pl->d_cert_win;
-            ka.cert_pub = pl->d_cert_pub;
-            ka.cert_pub_wgs = pl->cert_tile_wgs;
-            // the second round after promotions (MR_CERT_PROMOTE=0: none)
-            static const bool no_promote = [] {
-                const char *e = std::getenv("MR_CERT_PROMOTE");
-                return e && std::atoi(e) == 0;
-            }();
-            if (!no_promote && (pmalloc(reinterpret_cast<void **>(&pl->d_cert_redo), size_t(cap) * 4) != hipSuccess ||
-                                pmalloc(reinterpret_cast<void **>(&pl->d_args_r2), sizeof(KArgs)) != hipSuccess ||
-                                pmalloc(reinterpret_cast<void **>(&pl->d_args_cert_r2), sizeof(KArgs)) != hipSuccess))
-                return bail(fail(MR_ERR_DEVICE, "certificate slots"));
-        }
-        if (pl->n_lane && (pmalloc(reinterpret_cast<void **>(&pl->d_args_lane), sizeof(KArgs)) != hipSuccess ||
-                           pmalloc(reinterpret_cast<void **>(&pl->d_args_lane_last), sizeof(KArgs)) != hipSuccess))
-            return bail(fail(MR_ERR_DEVICE, "kernel args"));
-        if (relist) {
-            if (pmalloc(reinterpret_cast<void **>(&pl->d_relist), size_t(pl->n_lane) * 4) != hipSuccess)
-                return bail(fail(MR_ERR_DEVICE, "relist"));
-            ka.relist = pl->d_relist;
-        }
-        if (pl->n_lane) {  // the lane / group kernels' LDS block, built once per plan
-            const uint32_t TM = pl->lane_g ? pl->lane_g * hub_group_slots(NS, pl->lane_g) : hub_lane_entries(NS);
-            std::vector<uint32_t> blob;
-            lane_blob_build(hp.sp.data(), NS, hp.nreg, TM, hp.p.rgt, hp.p.ff_num, hp.p.ff_den, hp.near_sp.data(), blob);
-            if (upload(pl->d_lane_blob, blob) != MR_OK) return bail(fail(MR_ERR_DEVICE, "lane tables"));
-            ka.lane_blob = reinterpret_cast<const uint4 *>(pl->d_lane_blob);
+// all destinations, per source: a record per cell, the label table, the boundary ranks
+static int plan_all_outputs(mr_plan *pl, uint32_t n) {
+    const HostPlan &hp = pl->hp;
+    KArgs &ka = pl->ka;
+    mr_plan::Slot &k = pl->slots[0];
+    const size_t T = size_t(hp.p.NS) + 1, ns = std::max<size_t>(ka.nsrc, 1);
+    // rows padded to whole 128 B lines (rec_pitch; MR_REC_ALIGN=64 pads to whole
+    // 64-cell tile rows): the fill never stores part of a line
+    uint32_t align = 32;
+    if (const char *e = std::getenv("MR_REC_ALIGN"))
+        if (std::atoi(e) == 64) align = 64;
+    const uint32_t pitch = (hp.p.S + align - 1) / align * align;
+    ka.rec_pitch = pitch;
+    if (pl->out.rec.alloc(ns * hp.p.S * pitch) != hipSuccess || k.tab.alloc(ns * T) != hipSuccess ||
+        k.lex.alloc(ns * T) != hipSuccess || k.sstate.alloc(ns) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "hipMalloc all-destinations outputs");
+    ka.all_mode = 1;
+    ka.out_rec = pl->out.rec.get();
+    ka.early_exit_max = 0;  // every cell must settle
+    pl->src_of_input.assign(n, kNone32);
+    for (uint32_t si = 0; si < ka.nsrc; ++si)
+        for (uint32_t q = hp.q_begin[si]; q < hp.q_begin[si + 1]; ++q) pl->src_of_input[hp.q_id[q]] = si;
+    return MR_OK;
+}
+
+// hub plans: the fallback list, the region table (wide: its own tables), the launch
+// sizes and the argument blocks
+static int plan_hub(mr_plan *pl) {
+    HostPlan &hp = pl->hp;
+    KArgs &ka = pl->ka;
+    mr_plan::Hub &h = pl->hub;
+    mr_plan::Slot &k = pl->slots[0];
+    const uint32_t NS = hp.p.NS, nsrc = ka.nsrc;
+    if (k.fb.alloc(std::max<size_t>(nsrc, 1)) != hipSuccess) return fail(MR_ERR_DEVICE, "hub tables");
+    if (hp.near) {
+        ka.near = region_table_device(pl->grid, hp.homeland, pl->tab.rank);
+        if (!ka.near) return fail(MR_ERR_DEVICE, "region table build");
+        if (int st = special_rows_from_table(pl->grid, hp.homeland, ka.near, hp.nreg, hp.sp, hp.near_sp))
+            return fail(st, "region table rows");
+    }
+    if (hp.wide) {
+        std::vector<uint32_t> off(hp.rb_off->begin(), hp.rb_off->end());
+        if (off.empty()) off.push_back(0);
+        if (upload(h.near_sp, hp.near_sp) != hipSuccess || upload(h.rb_off, off) != hipSuccess ||
+            upload(h.rb_cell, *hp.rb_cell) != hipSuccess)
+            return fail(MR_ERR_DEVICE, "wide hub tables");
+        ka.near_sp = h.near_sp.get();
+        ka.rb_off = h.rb_off.get();
+        ka.rb_cell = h.rb_cell.get();
+    }
+    ka.nreg = hp.nreg;
+    // two sources per wave when the specials fit 32 lanes (MR_HUB_SPW=1 forces one);
+    // the wide kernel runs one source per wave
+    h.spw = !hp.wide && NS + 1 <= 32 ? 2u : 1u;
+    if (const char *e = std::getenv("MR_HUB_SPW"))
+        if (std::atoi(e) == 1) h.spw = 1;
+    const uint32_t hb = hp.wide ? hub_wide_lds_bytes(NS, hp.nreg) : hub_lds_bytes(NS, hp.nreg, h.spw);
+    if (hb > 160 * 1024) return fail(MR_ERR_LIMIT, "hub tables exceed LDS");
+    const int hper = std::max(1, hp.wide ? hub_wide_blocks_per_cu(hp.p.perm, NS, hb)
+                                         : hub_blocks_per_cu(hp.p.perm, h.spw, hp.nonlin, hb));
+    // (a lane kernel with Fleetfoot relists its uncertain sources for hub_kernel: room
+    // for a few hundred of them in one round)
+    const bool relist = h.n_lane && hp.nonlin;
+    const uint64_t per_block = 4ull * h.spw, hub_src = std::max<uint64_t>(nsrc - h.n_lane, relist ? 512u : 0u);
+    h.hub_blocks = resident_grid((hub_src + per_block - 1) / per_block, uint64_t(hper) * pl->cus);
+    if (const char *e = std::getenv("MR_HUB_BLOCKS")) h.hub_blocks = uint32_t(std::max(1, std::atoi(e)));
+    h.fb_blocks = pl->blocks;
+    h.fill_per_cu = uint32_t(std::max(1, fill_blocks_per_cu(hp.p.perm)));
+    if (k.args_fb.alloc(1) != hipSuccess || h.args_hub_last.alloc(1) != hipSuccess || k.args_fill.alloc(1) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "kernel args");
+    return MR_OK;
+}
+
+// Certified fallback for query plans on hub_kernel (MR_CERT=0: off; MR_CERT_SLOTS:
+// slots per pass, default by grid size): a flagged source's table goes to a slot, the fill
+// writes its closed form over every cell, the check and one repair sweep decide
+// whether its labels need the SSSP kernel at all.
+static int plan_cert(mr_plan *pl) {
+    const HostPlan &hp = pl->hp;
+    if (pl->all_mode || hp.wide || env_is("MR_CERT", "0")) return MR_OK;
+    KArgs &ka = pl->ka;
+    mr_plan::Cert &c = pl->cert;
+    const uint32_t V = hp.p.V;
+    // slots: as many as 512 MB of cell words and sweep lists hold, 8 to 64 (1025^2:
+    // 60; 4097^2: 8).  A Time-first Fleetfoot 1 batch of 125k on c4's map hands
+    // over ~40 sources, and every one without a slot costs a whole SSSP solve.
+    const size_t T = size_t(hp.p.NS) + 1, ns = std::max<size_t>(ka.nsrc, 1);
+    const uint32_t pitch = (hp.p.S + 31) / 32 * 32;
+    const size_t slot_bytes = size_t(V) * 4 + size_t(hp.p.S) * pitch * 4 + T * (sizeof(Rec) + 4);
+    uint32_t cap = uint32_t(std::min<size_t>(64, std::max<size_t>(8, (size_t(512) << 20) / slot_bytes)));
+    if (const char *e = std::getenv("MR_CERT_SLOTS")) cap = uint32_t(std::min(64, std::max(1, std::atoi(e))));
+    // staging for every fallback entry up to kCertStageMax (mr_engine.hpp): a
+    // pass with more hands nothing to the certificate
+    const uint32_t stage = uint32_t(std::min<size_t>(kCertStageMax, ns));
+    if (c.stage_tab.alloc(stage * T) != hipSuccess || c.stage_lex.alloc(stage * T) != hipSuccess ||
+        c.stage_src.alloc(stage) != hipSuccess || c.tab.alloc(cap * T) != hipSuccess || c.lex.alloc(cap * T) != hipSuccess ||
+        c.src.alloc(cap) != hipSuccess || c.aux.alloc(size_t(cap) * V) != hipSuccess ||
+        c.rec.alloc(size_t(cap) * hp.p.S * pitch) != hipSuccess || c.fb.alloc(ns) != hipSuccess ||
+        c.args.alloc(1) != hipSuccess || upload(c.ones, std::vector<uint32_t>(cap, 1u)) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "certificate slots");
+    c.cap = cap;
+    // (a workgroup's four waves a tile each, for every slot: the fill spreads the slots
+    // over groups of waves, and workgroups past the slots in use exit.  One slot's
+    // worth of workgroups left a small grid's 8 slots to 3 workgroups, one after the
+    // other: 0.34 ms of Fleetfoot fill at 65^2)
+    c.fill_gx = resident_grid((fill_tiles(hp.p.S) + 3) / 4 * cap, uint64_t(pl->hub.fill_per_cu) * pl->cus);
+    c.check_gx = resident_grid((uint64_t(V) + 4 * 256 - 1) / (4 * 256), 4ull * pl->cus);
+    // the check's state: one partial per slot and check workgroup, reduced by its readers
+    if (c.st.alloc(size_t(cap) * c.check_gx * kCertSt) != hipSuccess) return fail(MR_ERR_DEVICE, "certificate slots");
+    // the repair: per slot its window; the tile sweep's persistent grid (one
+    // workgroup a CU, each with two publish areas).  MR_CERT_TILE=0: the round-5
+    // sweep for every slot (A/B); MR_CERT_PROMOTE=0: no second round (both read once)
+    static const bool no_tile = env_zero("MR_CERT_TILE"), no_promote = env_zero("MR_CERT_PROMOTE");
+    const int occ = no_tile ? 0 : cert_tile_occupancy();
+    c.tile_wgs = occ > 0 ? uint32_t(occ) * pl->cus : 0u;
+    // (+ one word: cert_window_kernel's completion count, zero between launches)
+    if (c.win.alloc_zero(size_t(cap) * kWinWords + 1) != hipSuccess ||
+        (c.tile_wgs && c.pub.alloc(size_t(c.tile_wgs) * 2 * kTileT * kTileT) != hipSuccess))
+        return fail(MR_ERR_DEVICE, "certificate slots");
+    // the second round after promotions
+    if (!no_promote &&
+        (c.redo.alloc(cap) != hipSuccess || c.args_r2.alloc(1) != hipSuccess || c.args_cert_r2.alloc(1) != hipSuccess))
+        return fail(MR_ERR_DEVICE, "certificate slots");
+    ka.cert_cap = cap;
+    ka.cert_stage_cap = stage;
+    ka.cert_stage_tab = c.stage_tab.get();
+    ka.cert_stage_lex = c.stage_lex.get();
+    ka.cert_stage_src = c.stage_src.get();
+    ka.cert_tab = c.tab.get();
+    ka.cert_lex = c.lex.get();
+    ka.cert_src = c.src.get();
+    ka.cert_st = c.st.get();
+    ka.cert_aux = c.aux.get();
+    ka.cert_rec = c.rec.get();
+    ka.fb_cert = c.fb.get();
+    ka.rec_pitch = pitch;
+    ka.cert_parts = c.check_gx;
+    ka.cert_win = c.win.get();
+    ka.cert_pub = c.pub.get();
+    ka.cert_pub_wgs = c.tile_wgs;
+    return MR_OK;
+}
+
+// the lane / group kernels' argument blocks, relist and LDS block (built once per plan)
+static int plan_lane(mr_plan *pl) {
+    const HostPlan &hp = pl->hp;
+    KArgs &ka = pl->ka;
+    mr_plan::Hub &h = pl->hub;
+    if (!h.n_lane) return MR_OK;
+    const uint32_t NS = hp.p.NS;
+    if (h.args_lane.alloc(1) != hipSuccess || h.args_lane_last.alloc(1) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "kernel args");
+    if (hp.nonlin) {
+        if (h.relist.alloc(h.n_lane) != hipSuccess) return fail(MR_ERR_DEVICE, "relist");
+        ka.relist = h.relist.get();
+    }
+    const uint32_t TM = h.lane_g ? h.lane_g * hub_group_slots(NS, h.lane_g) : hub_lane_entries(NS);
+    std::vector<uint32_t> blob;
+    lane_blob_build(hp.sp.data(), NS, hp.nreg, TM, hp.p.rgt, hp.p.ff_num, hp.p.ff_den, hp.near_sp.data(), blob);
+    if (upload(h.lane_blob, blob) != hipSuccess) return fail(MR_ERR_DEVICE, "lane tables");
+    ka.lane_blob = reinterpret_cast<const uint4 *>(h.lane_blob.get());
+    return MR_OK;
+}
+
+// The lane memo (DESIGN.md section 3a'''): where the gate holds, the lane kernel's
+// sources read their destinations off rows built once per (grid, params).
+// MR_LANE_MEMO=0: never; =require: plan creation fails where the gate is false
+// (tests tell the path that ran this way).
+static int plan_lane_memo(mr_plan *pl) {
+    const HostPlan &hp = pl->hp;
+    std::string why = "switched off";
+    if (!env_is("MR_LANE_MEMO", "0")) {
+        if (!hp.hub || !pl->hub.n_lane || pl->hub.lane_g) why = "not a lane plan";
+        else if (hub_lane_entries(hp.p.NS) != 22) why = "a table of more than 22 entries";
+        else if (hp.nonlin) why = "non-linear run times";
+        else {
+            pl->hub.memo = lane_memo_rows(pl->grid, pl->device, hp, slot_args(pl, 0), pl->stream.get());
+            if (!pl->hub.memo) return fail(MR_ERR_DEVICE, "lane memo rows");
+            if (pl->hub.memo->gate) pl->ka.lane_memo = pl->hub.memo->d_rows.get();
+            else why = pl->hub.memo->why;
         }
     }
-    {
-        // The lane memo (DESIGN.md section 3a'''): where the gate holds, the lane kernel's
-        // sources read their destinations off rows built once per (grid, params).
-        // MR_LANE_MEMO=0: never; =require: plan creation fails where the gate is false
-        // (tests tell the path that ran this way).
-        const char *lm = std::getenv("MR_LANE_MEMO");
-        const bool memo_off = lm && !std::strcmp(lm, "0"), memo_req = lm && !std::strcmp(lm, "require");
-        std::string why = "switched off";
-        if (!memo_off) {
-            if (!hp.hub || !pl->n_lane || pl->lane_g) why = "not a lane plan";
-            else if (hub_lane_entries(NS) != 22) why = "a table of more than 22 entries";
-            else if (hp.nonlin) why = "non-linear run times";
-            else {
-                pl->memo = lane_memo_rows(g, pl->device, hp, ka, pl->stream);
-                if (!pl->memo) return bail(fail(MR_ERR_DEVICE, "lane memo rows"));
-                if (pl->memo->gate) ka.lane_memo = pl->memo->d_rows;
-                else why = pl->memo->why;
-            }
-        }
-        if (memo_req && !ka.lane_memo) return bail(fail(MR_ERR_INVALID_ARG, "MR_LANE_MEMO=require: " + why));
-    }
+    if (env_is("MR_LANE_MEMO", "require") && !pl->ka.lane_memo)
+        return fail(MR_ERR_INVALID_ARG, "MR_LANE_MEMO=require: " + why);
+    return MR_OK;
+}
+
+// diagnostic builds: the buffer the kernels stamp (a failed allocation leaves it off)
+static void plan_diag(mr_plan *pl) {
 #ifdef MR_HUBDUMP
     if (const char *e = std::getenv("MR_DEBUG_SRC"))
-        if (pmalloc(reinterpret_cast<void **>(&pl->d_dbg), 64 * 16 * 4) == hipSuccess) {
-            (void)hipMemset(pl->d_dbg, 0, 64 * 16 * 4);
-            ka.dbg = pl->d_dbg;
-            ka.dbg_blocks = uint32_t(std::atoi(e));
+        if (pl->out.dbg.alloc_zero(64 * 16 / 2) == hipSuccess) {
+            pl->ka.dbg = pl->out.dbg.get();
+            pl->ka.dbg_blocks = uint32_t(std::atoi(e));
         }
 #endif
 #ifdef MR_STAMPS
-    if (pmalloc(reinterpret_cast<void **>(&pl->d_dbg), (size_t(pl->blocks) * 10 + 16) * 8) == hipSuccess) {
-        (void)hipMemset(pl->d_dbg, 0, (size_t(pl->blocks) * 10 + 16) * 8);
-        ka.dbg = pl->d_dbg;
-        ka.dbg_blocks = pl->blocks;
+    if (pl->out.dbg.alloc_zero(size_t(pl->blocks) * 10 + 16) == hipSuccess) {
+        pl->ka.dbg = pl->out.dbg.get();
+        pl->ka.dbg_blocks = pl->blocks;
     }
 #endif
-    if (pmalloc(reinterpret_cast<void **>(&pl->d_args), sizeof(KArgs)) != hipSuccess || upload_args(pl) != MR_OK)
-        return bail(fail(MR_ERR_DEVICE, "kernel args"));
-    // all destinations with the hub: slots of per-pass buffers, so that the specials'
-    // solves of the next passes overlap this pass's fill (MR_FILL_OVERLAP=0: off;
-    // MR_FILL_SLOTS: the slot count, 2..8, default 2 — at c3 the specials' solve of a
-    // pass is shorter than a fill, and 3 or 4 slots measured the same pass time)
-    const char *ov = std::getenv("MR_FILL_OVERLAP");
-    if (all_mode && hp.hub && !(ov && !std::strcmp(ov, "0"))) {
-        uint32_t nslots = 2;
-        if (const char *e = std::getenv("MR_FILL_SLOTS")) nslots = uint32_t(std::min(8, std::max(2, std::atoi(e))));
-        const size_t T = size_t(NS) + 1, ns = std::max<size_t>(nsrc, 1);
-        pl->slots.resize(nslots);
-        mr_plan::Slot &k0 = pl->slots[0];
-        k0.tab = pl->d_tab;
-        k0.lex = pl->d_lex;
-        k0.sstate = pl->d_sstate;
-        k0.fb = pl->d_fb;
-        k0.counter = pl->d_counter;
-        k0.args = pl->d_args;
-        k0.args_fb = pl->d_args_fb;
-        k0.args_fill = pl->d_args_fill;
-        for (uint32_t i = 0; i < nslots; ++i) {
-            mr_plan::Slot &k = pl->slots[i];
-            if (i > 0 &&
-                (pmalloc(reinterpret_cast<void **>(&k.tab), ns * T * sizeof(Rec)) != hipSuccess ||
-                 pmalloc(reinterpret_cast<void **>(&k.lex), ns * T * 4) != hipSuccess ||
-                 pmalloc(reinterpret_cast<void **>(&k.sstate), ns * 4) != hipSuccess ||
-                 pmalloc(reinterpret_cast<void **>(&k.fb), ns * 4) != hipSuccess ||
-                 pmalloc(reinterpret_cast<void **>(&k.counter), kCtrWords * 4) != hipSuccess ||
-                 hipMemset(k.counter, 0, kCtrWords * 4) != hipSuccess ||
-                 pmalloc(reinterpret_cast<void **>(&k.args), sizeof(KArgs)) != hipSuccess ||
-                 pmalloc(reinterpret_cast<void **>(&k.args_fb), sizeof(KArgs)) != hipSuccess ||
-                 pmalloc(reinterpret_cast<void **>(&k.args_fill), sizeof(KArgs)) != hipSuccess))
-                return bail(fail(MR_ERR_DEVICE, "all-destinations slots"));
-            if (hipEventCreateWithFlags(&k.ev_hub, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&k.ev_fill, hipEventDisableTiming) != hipSuccess)
-                return bail(fail(MR_ERR_DEVICE, "overlap streams"));
-            if (i > 0) {
-                use_slot(pl, i);
-                const int ua = upload_args(pl);
-                use_slot(pl, 0);
-                if (ua != MR_OK) return bail(fail(MR_ERR_DEVICE, "kernel args"));
-            }
-        }
-        if (pstream_create(&pl->hub_stream) != hipSuccess)
-            return bail(fail(MR_ERR_DEVICE, "hub stream"));
-        pl->overlap = true;
-        const char *fz = std::getenv("MR_FILL_FUSED");
-        if (!hp.wide && !hp.nonlin && !(fz && !std::strcmp(fz, "0"))) {
-            pl->hub_lds = hub_lds_bytes(NS, hp.nreg, pl->spw);
-            pl->fused_per_cu = uint32_t(std::max(0, hub_fill_blocks_per_cu(hp.p.perm, pl->spw, pl->hub_lds)));
-            pl->fused = pl->fused_per_cu > 0;
-        }
+}
+
+// all destinations with the hub: slots of per-pass buffers, so that the specials'
+// solves of the next passes overlap this pass's fill (MR_FILL_OVERLAP=0: off;
+// MR_FILL_SLOTS: the slot count, 2..8, default 2 — at c3 the specials' solve of a
+// pass is shorter than a fill, and 3 or 4 slots measured the same pass time)
+static int plan_overlap(mr_plan *pl) {
+    const HostPlan &hp = pl->hp;
+    if (!pl->all_mode || !hp.hub || env_is("MR_FILL_OVERLAP", "0")) return MR_OK;
+    uint32_t nslots = 2;
+    if (const char *e = std::getenv("MR_FILL_SLOTS")) nslots = uint32_t(std::min(8, std::max(2, std::atoi(e))));
+    const size_t T = size_t(hp.p.NS) + 1, ns = std::max<size_t>(pl->ka.nsrc, 1);
+    pl->slots.resize(nslots);
+    for (uint32_t i = 0; i < nslots; ++i) {
+        mr_plan::Slot &k = pl->slots[i];
+        if (i > 0 && (k.tab.alloc(ns * T) != hipSuccess || k.lex.alloc(ns * T) != hipSuccess ||
+                      k.sstate.alloc(ns) != hipSuccess || k.fb.alloc(ns) != hipSuccess ||
+                      k.counter.alloc_zero(kCtrWords) != hipSuccess || k.args.alloc(1) != hipSuccess ||
+                      k.args_fb.alloc(1) != hipSuccess || k.args_fill.alloc(1) != hipSuccess))
+            return fail(MR_ERR_DEVICE, "all-destinations slots");
+        if (k.ev_hub.create(hipEventDisableTiming) != hipSuccess || k.ev_fill.create(hipEventDisableTiming) != hipSuccess)
+            return fail(MR_ERR_DEVICE, "overlap streams");
+        if (i > 0 && upload_args(pl, i) != MR_OK) return fail(MR_ERR_DEVICE, "kernel args");
     }
+    if (pl->hub_stream.create() != hipSuccess) return fail(MR_ERR_DEVICE, "hub stream");
+    pl->overlap = true;
+    if (!hp.wide && !hp.nonlin && !env_is("MR_FILL_FUSED", "0")) {
+        pl->hub_lds = hub_lds_bytes(hp.p.NS, hp.nreg, pl->hub.spw);
+        pl->fused_per_cu = uint32_t(std::max(0, hub_fill_blocks_per_cu(hp.p.perm, pl->hub.spw, pl->hub_lds)));
+        pl->fused = pl->fused_per_cu > 0;
+    }
+    return MR_OK;
+}
+
+static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *qs, uint32_t n, uint32_t max_cmds,
+                       mr_plan **out, bool all_mode = false) {
+    if (!out || (n && !qs)) return fail(MR_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!mr_device_available()) return fail(MR_ERR_NO_DEVICE, "no gfx950 device visible (no CPU fallback)");
+    const double tm0 = timing_on() ? now_ms() : 0.0;
+    double tm_build = 0, tm_upload = 0, tm_alloc = 0;
+    // (a creation that fails gives back, through the members' destructors, whatever the
+    // steps so far took; every step that queues device work waits for it before it returns)
+    std::unique_ptr<mr_plan> pl(new mr_plan());
+    pl->grid = g;
+    pl->all_mode = all_mode;
+    HostPlan &hp = pl->hp;
+    int st = build_plan(g, prm, qs, n, max_cmds, hp, !all_mode);
+    if (st == MR_OK && hp.dev_grouped) {  // the batch grouped on the device (counts back)
+        if (hipGetDevice(&pl->device) != hipSuccess) st = fail(MR_ERR_DEVICE, "hipGetDevice");
+        else if (pl->stream.create() != hipSuccess) st = fail(MR_ERR_DEVICE, "stream");
+        else st = group_on_device(pl.get(), qs, n);
+    }
+    if (timing_on()) tm_build = now_ms();
+    if (st != MR_OK) return st;
+    // all destinations: hub_kernel + fill only, linear run times (the fill's keys)
+    if (all_mode && (hp.wide || hp.nonlin)) hp.hub = hp.wide = hp.nonlin = false;
+    if ((st = plan_partition(pl.get(), choose_kernel(hp, all_mode))) || (st = plan_tables(pl.get())) ||
+        (st = plan_batch_upload(pl.get())))
+        return st;
+    if (timing_on()) tm_upload = now_ms();
+    if ((st = plan_outputs(pl.get(), n, max_cmds))) return st;
+    if (timing_on()) tm_alloc = now_ms();
+    if (pl->stream.create() != hipSuccess) return fail(MR_ERR_DEVICE, "stream");
+    plan_base_args(pl.get(), n);
+    if (all_mode && (st = plan_all_outputs(pl.get(), n))) return st;
+    if (hp.hub && ((st = plan_hub(pl.get())) || (st = plan_cert(pl.get())) || (st = plan_lane(pl.get())))) return st;
+    if ((st = plan_lane_memo(pl.get()))) return st;
+    plan_diag(pl.get());
+    if (pl->slots[0].args.alloc(1) != hipSuccess || upload_args(pl.get()) != MR_OK) return fail(MR_ERR_DEVICE, "kernel args");
+    if ((st = plan_overlap(pl.get()))) return st;
     if (timing_on())
         std::fprintf(stderr, "MR_TIMING plan_create n=%u: build %.2f ms, upload %.2f, outputs+workspace %.2f, rest %.2f\n", n,
                      tm_build - tm0, tm_upload - tm_build, tm_alloc - tm_upload, now_ms() - tm_alloc);
-    *out = pl;
+    *out = pl.release();
     return MR_OK;
 }
 
@@ -2857,193 +2622,198 @@ extern "C" int mr_plan_create_ex(const mr_grid *g, const mr_params *prm, const m
 
 
 static hipError_t launch_hub_plan(const mr_plan *pl, const KArgs *d_args, hipStream_t s) {
-    if (pl->hp.wide) return launch_hub_wide(d_args, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->hub_blocks, s);
-    return launch_hub(d_args, pl->ka.p.perm, pl->spw, pl->hp.nonlin, pl->ka.p.NS, pl->ka.nreg, pl->hub_blocks, s);
+    if (pl->hp.wide) return launch_hub_wide(d_args, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->hub.hub_blocks, s);
+    return launch_hub(d_args, pl->ka.p.perm, pl->hub.spw, pl->hp.nonlin, pl->ka.p.NS, pl->ka.nreg, pl->hub.hub_blocks, s);
+}
+static hipError_t launch_fallback(const mr_plan *pl, const mr_plan::Slot &k, hipStream_t s) {
+    return launch_solve(k.args_fb.get(), pl->grid_in_lds, pl->algo, pl->ka.p.NS, pl->ka.p.V, pl->hub.fb_blocks, s);
 }
 
 static void fold_timed(mr_plan *pl, size_t keep);
 static constexpr size_t kMaxTimed = 1024;  // pending timing event pairs per plan
 
+// a fill launch's start event, recorded on s (an empty one where it cannot be created)
+static Event fill_start(hipStream_t s) {
+    Event f0;
+    if (f0.create() == hipSuccess) (void)hipEventRecord(f0.get(), s);
+    return f0;
+}
+
+// (source, tile) items of an all-destinations fill, one per wave
+static uint64_t fill_items(const mr_plan *pl) { return uint64_t(pl->ka.nsrc) * fill_tiles(pl->ka.p.S); }
+
+// Fused all-destinations pass: this pass's specials were solved into its slot by the
+// previous pass's launch (the first pass solves its own first).  The SSSP kernel takes the
+// sources that solve flagged, then one launch fills this pass's cells while its
+// first workgroups solve the next pass's specials into the next slot (which the
+// previous launch's fill has finished reading: stream order).  Each pass thus runs
+// one specials' solve and one fill; the last pass's look-ahead solve is extra work.
+static hipError_t run_fused(mr_plan *pl, uint32_t prev_slot, hipStream_t s) {
+    const uint32_t nslots = uint32_t(pl->slots.size()), cur = pl->slot, nxt = (cur + 1) % nslots;
+    const uint64_t resident = uint64_t(pl->fused_per_cu) * pl->cus;
+    // the look-ahead solve takes at most a quarter of the resident workgroups: with
+    // as many hub workgroups as fit (8 k+ sources a pass at 1025^2) the fill was left
+    // with one workgroup (12 288 sources: 4.3 s a pass; 17 ms with 256 fill workgroups)
+    const uint32_t hub_fused = resident_grid(pl->hub.hub_blocks, std::max<uint64_t>(1, resident / 4));
+    const uint32_t fb_blocks = resident_grid((fill_items(pl) + 3) / 4, resident > hub_fused ? resident - hub_fused : 1);
+    hipError_t e = hipSuccess;
+    // the first pass (or one after a failed launch) solves its own specials first
+    const bool solve_own = !pl->slots[cur].solved;
+    if (solve_own) e = launch_hub_plan(pl, pl->slots[cur].args.get(), s);
+    if (e == hipSuccess) pl->slots[cur].solved = true;
+    if (e == hipSuccess && !pl->fb_none) e = launch_fallback(pl, pl->slots[cur], s);
+    // with no SSSP launch the pass is the fused launch: its time is the pass's (an
+    // event of its own costs command-processor time, see ev_last below)
+    const bool own = solve_own || !pl->fb_none;
+    Event f0;
+    if (e == hipSuccess && own) f0 = fill_start(s);
+    if (e == hipSuccess)
+        e = launch_hub_fill(pl->slots[nxt].args.get(), pl->slots[cur].args_fill.get(), pl->ka.p.perm, pl->hub.spw, hub_fused,
+                            fb_blocks, pl->hub_lds, s);
+    if (e == hipSuccess) {
+        pl->slots[cur].used = true;  // a fill ran in it: its counters hold a finished pass
+        pl->slots[nxt].solved = true;
+    } else {
+        // nothing of this pass is trusted: the next run re-takes this slot, and the
+        // slot the failed launch may have half-written is solved again
+        pl->slots[nxt].solved = false;
+        --pl->runs;
+        pl->slot = prev_slot;
+        if (pl->runs == 0) pl->slots[cur].solved = false;
+    }
+    pl->timed_fill.push_back({std::move(f0), nullptr, !own});
+    return e;
+}
+
+// All-destinations pass in three launches: hub solve + table export, the SSSP kernel for
+// flagged sources, then the fill: (source, tile) items, one per wave, over a
+// resident-sized grid.  Overlap: this pass took its slot in mr_plan_run, and its hub kernel
+// runs on the hub stream behind the wait for the fill that last read the slot.  The hub
+// writes only the slot's tables; everything that writes the records (the SSSP kernel for
+// flagged sources, the fill) stays on the caller's stream, in stream order.
+static hipError_t run_all(mr_plan *pl, hipStream_t s) {
+    const mr_plan::Slot &k = pl->cur();
+    uint32_t gx = resident_grid((fill_items(pl) + 3) / 4, uint64_t(pl->hub.fill_per_cu) * pl->cus);
+    if (const char *e = std::getenv("MR_FILL_GX")) gx = uint32_t(std::max(1, std::atoi(e)));
+    const hipStream_t hs = pl->overlap ? pl->hub_stream.get() : s;
+    hipError_t e = launch_hub_plan(pl, k.args.get(), hs);
+    if (e == hipSuccess && pl->overlap &&
+        (hipEventRecord(k.ev_hub.get(), hs) != hipSuccess || hipStreamWaitEvent(s, k.ev_hub.get(), 0) != hipSuccess))
+        e = hipErrorUnknown;
+    if (e == hipSuccess && !pl->fb_none) e = launch_fallback(pl, k, s);
+    Event f0;
+    if (e == hipSuccess) f0 = fill_start(s);
+    if (e == hipSuccess) e = launch_fill(k.args_fill.get(), pl->ka.p.perm, gx, 1, s);
+    // the slot's tables are free again once this fill has read them
+    if (e == hipSuccess && pl->overlap && hipEventRecord(k.ev_fill.get(), s) != hipSuccess) e = hipErrorUnknown;
+    pl->timed_fill.push_back({std::move(f0), nullptr, false});  // one per pass (f0 may be empty), as in `timed`
+    return e;
+}
+
+// the certificate's repair of the slots `args` names, after a check that marked their
+// failing cells (the sweep's seeds): each slot's window, the tile sweep (Legs / Time
+// first), the round-5 sweep for the others, the check again
+static hipError_t cert_repair(const mr_plan *pl, const KArgs *args, hipStream_t s) {
+    const mr_plan::Cert &c = pl->cert;
+    hipError_t e = launch_cert_window(args, c.cap, s);
+    if (e == hipSuccess && c.tile_wgs) e = launch_cert_tile(args, c.tile_wgs, s);
+    if (e == hipSuccess) e = launch_cert_sweep(args, c.cap, s);
+    if (e == hipSuccess) e = launch_cert_check(args, c.check_gx, c.cap, 0u, s);
+    return e;
+}
+
+// Query pass of a hub plan.  Closed-form hub solve: the lane kernel for the sources with
+// few queries, the hub kernel for the others, then the SSSP kernel for the sources they
+// flagged (usually none; those workgroups exit at once).  Once a pass of this plan (same
+// inputs, deterministic result) had no fallback source, the hub launches end the pass on
+// their own.  (A Fleetfoot lane plan relaunches hub_kernel for the sources its lane kernel
+// relisted, until a pass had none.)
+static hipError_t run_hub(mr_plan *pl, hipStream_t s) {
+    const mr_plan::Hub &h = pl->hub;
+    const mr_plan::Cert &c = pl->cert;
+    const mr_plan::Slot &k = pl->cur();
+    const KArgs *args = k.args.get();
+    const uint32_t *perm = pl->ka.p.perm, NS = pl->ka.p.NS, nreg = pl->ka.nreg;
+    const bool big = pl->ka.nsrc > h.n_lane || (h.relist && !pl->fb_none);
+    hipError_t e = hipSuccess;
+    if (h.n_lane) {
+        const KArgs *la = (pl->fb_none && !big ? h.args_lane_last : h.args_lane).get();
+        // (a plan whose memo gate held: the destinations only, from the grid's rows)
+        if (h.lane_g) e = launch_hub_group(la, perm, NS, nreg, h.n_lane, h.lane_g, pl->hp.nonlin, s);
+        else if (pl->ka.lane_memo) e = launch_hub_lane_memo(la, perm, NS, nreg, h.n_lane, s);
+        else e = launch_hub_lane(la, perm, NS, nreg, h.n_lane, pl->hp.nonlin, s);
+    }
+    if (e == hipSuccess && big) e = launch_hub_plan(pl, pl->fb_none ? h.args_hub_last.get() : args, s);
+    // certified fallback: the slots given to the staged sources in source order,
+    // their closed forms, the check, one repair sweep, the check again (each exits at
+    // once without slots); the SSSP launch then
+    // emits every certified source from its slot and solves the rest
+    if (e == hipSuccess && !pl->fb_none && c.cap) {
+        e = launch_cert_select(args, s);
+        if (e == hipSuccess) e = launch_fill(c.args.get(), perm, c.fill_gx, 1, s);
+        // (MR_CERT_NOSWEEP=1: diagnostics, the first check's state stays for MR_CERT_DEBUG)
+        static const bool nosweep = std::getenv("MR_CERT_NOSWEEP") != nullptr;
+        if (e == hipSuccess) e = launch_cert_check(args, c.check_gx, c.cap, nosweep ? 0u : 1u, s);
+        if (!nosweep) {
+            if (e == hipSuccess) e = cert_repair(pl, args, s);
+            // further rounds for the slots whose last check still failed: the closed form
+            // again after a promotion, else the sweep again from the repaired words
+            for (int round = 0; round < kCertRounds && e == hipSuccess && c.args_r2; ++round) {
+                e = launch_cert_promote(args, c.cap, c.redo.get(), s);
+                if (e == hipSuccess) e = launch_fill(c.args_cert_r2.get(), perm, c.fill_gx, 1, s);
+                if (e == hipSuccess) e = launch_cert_check(c.args_r2.get(), c.check_gx, c.cap, 1u, s);
+                if (e == hipSuccess) e = cert_repair(pl, c.args_r2.get(), s);
+            }
+        }
+    }
+    if (e == hipSuccess && !pl->fb_none) e = launch_fallback(pl, k, s);
+    return e;
+}
+
 extern "C" int mr_plan_run(mr_plan *pl, void *stream) {
     if (!pl) return fail(MR_ERR_INVALID_ARG, "null plan");
-    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : pl->stream;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : pl->stream.get();
     if (pl->ka.nsrc == 0) return MR_OK;
     if (pl->timed.size() >= kMaxTimed) fold_timed(pl, kMaxTimed / 4);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess) return fail(MR_ERR_DEVICE, "event");
-    if (hipEventCreate(&e1) != hipSuccess) {
-        (void)hipEventDestroy(e0);
-        return fail(MR_ERR_DEVICE, "event");
-    }
+    Event e0, e1;
+    if (e0.create() != hipSuccess || e1.create() != hipSuccess) return fail(MR_ERR_DEVICE, "event");
     // Passes of one plan run in submission order whatever streams they are given:
     // a pass reads what the previous one left (the fused look-ahead tables, the
     // counters it resets, a slot the previous fill read), so a pass on another stream
     // first waits for the previous pass's end.  plan_sync then only needs the last.
-    if (pl->ev_last && pl->last_stream != s && hipStreamWaitEvent(s, pl->ev_last, 0) != hipSuccess) {
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
+    if (pl->ev_last && pl->last_stream != s && hipStreamWaitEvent(s, pl->ev_last, 0) != hipSuccess)
         return fail(MR_ERR_DEVICE, "wait for the previous pass");
-    }
+    const bool all_hub = pl->hp.hub && pl->all_mode;
     const uint32_t prev_slot = pl->slot;
-    if (pl->hp.hub && pl->all_mode && pl->fused) {  // one launch per pass, see below
-        const uint32_t cur = pl->runs >= 1 ? (pl->slot + 1) % uint32_t(pl->slots.size()) : 0u;
-        use_slot(pl, cur);
-    } else if (pl->hp.hub && pl->all_mode && pl->overlap) {
+    if (all_hub && pl->fused) {  // one launch per pass (run_fused)
+        pl->slot = pl->next_slot();
+    } else if (all_hub && pl->overlap) {
         // overlap plans: this pass takes the next slot once the fill that last read it
         // has released it; nothing is launched or recorded before that wait is in place
-        const uint32_t prev = pl->slot, next = pl->runs >= 1 ? (pl->slot + 1) % uint32_t(pl->slots.size()) : 0u;
-        use_slot(pl, next);
-        if (pl->slots[next].used && hipStreamWaitEvent(pl->hub_stream, pl->slots[next].ev_fill, 0) != hipSuccess) {
-            use_slot(pl, prev);
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
+        mr_plan::Slot &k = pl->slots[pl->next_slot()];
+        if (k.used && hipStreamWaitEvent(pl->hub_stream.get(), k.ev_fill.get(), 0) != hipSuccess)
             return fail(MR_ERR_DEVICE, "wait");
-        }
-        pl->slots[next].used = true;
+        pl->slot = pl->next_slot();
+        k.used = true;
     }
-    (void)hipEventRecord(e0, s);
-    hipError_t e;
+    (void)hipEventRecord(e0.get(), s);
     ++pl->runs;
-    if (pl->hp.hub && pl->all_mode && pl->fused) {
-        // Fused: this pass's specials were solved into its slot by the previous pass's
-        // launch (the first pass solves its own first).  The SSSP kernel takes the
-        // sources that solve flagged, then one launch fills this pass's cells while its
-        // first workgroups solve the next pass's specials into the next slot (which the
-        // previous launch's fill has finished reading: stream order).  Each pass thus runs
-        // one specials' solve and one fill; the last pass's look-ahead solve is extra work.
-        const uint32_t nslots = uint32_t(pl->slots.size()), cur = pl->slot, nxt = (cur + 1) % nslots;
-        const uint64_t items = uint64_t(pl->ka.nsrc) * ((pl->ka.p.S + kFillTW - 1) / kFillTW) *
-                               ((pl->ka.p.S + kFillTH - 1) / kFillTH);
-        const uint64_t resident = uint64_t(pl->fused_per_cu) * pl->cus;
-        // the look-ahead solve takes at most a quarter of the resident workgroups: with
-        // as many hub workgroups as fit (8 k+ sources a pass at 1025^2) the fill was left
-        // with one workgroup (12 288 sources: 4.3 s a pass; 17 ms with 256 fill workgroups)
-        const uint32_t hub_fused = uint32_t(std::min<uint64_t>(pl->hub_blocks, std::max<uint64_t>(1, resident / 4)));
-        const uint32_t fb_blocks = uint32_t(std::max<uint64_t>(
-            1, std::min<uint64_t>((items + 3) / 4, resident > hub_fused ? resident - hub_fused : 1)));
-        e = hipSuccess;
-        // the first pass (or one after a failed launch) solves its own specials first
-        const bool solve_own = !pl->slots[cur].solved;
-        if (solve_own) e = launch_hub_plan(pl, pl->slots[cur].args, s);
-        if (e == hipSuccess) pl->slots[cur].solved = true;
-        if (e == hipSuccess && !pl->fb_none)
-            e = launch_solve(pl->d_args_fb, pl->grid_in_lds, pl->algo, pl->ka.p.NS, pl->ka.p.V, pl->fb_blocks, s);
-        // with no SSSP launch the pass is the fused launch: its time is the pass's (an
-        // event of its own costs command-processor time, see ev_last below)
-        hipEvent_t f0 = nullptr;
-        const bool own = solve_own || !pl->fb_none;
-        if (e == hipSuccess && own && hipEventCreate(&f0) == hipSuccess) (void)hipEventRecord(f0, s);
-        if (e == hipSuccess)
-            e = launch_hub_fill(pl->slots[nxt].args, pl->slots[cur].args_fill, pl->ka.p.perm, pl->spw, hub_fused,
-                                fb_blocks, pl->hub_lds, s);
-        if (e == hipSuccess) {
-            pl->slots[cur].used = true;  // a fill ran in it: its counters hold a finished pass
-            pl->slots[nxt].solved = true;
-        } else {
-            // nothing of this pass is trusted: the next run re-takes this slot, and the
-            // slot the failed launch may have half-written is solved again
-            pl->slots[nxt].solved = false;
-            --pl->runs;
-            use_slot(pl, prev_slot);
-            if (pl->runs == 0) pl->slots[cur].solved = false;
-        }
-        pl->timed_fill.push_back({f0, nullptr, !own});
-    } else if (pl->hp.hub && pl->all_mode) {
-        // hub solve + table export, the SSSP kernel for flagged sources, then the fill:
-        // (source, tile) items, one per wave, over a resident-sized grid
-        const uint64_t items = uint64_t(pl->ka.nsrc) * ((pl->ka.p.S + kFillTW - 1) / kFillTW) *
-                               ((pl->ka.p.S + kFillTH - 1) / kFillTH);
-        uint32_t gx = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((items + 3) / 4, uint64_t(pl->fill_per_cu) * pl->cus)));
-        if (const char *e = std::getenv("MR_FILL_GX")) gx = uint32_t(std::max(1, std::atoi(e)));
-        const uint32_t gy = 1;
-        // overlap: this pass took its slot above, and its hub kernel runs on the slot's
-        // stream behind the wait for the fill that last read the slot.  The hub writes
-        // only the slot's tables; everything that writes the records (the SSSP kernel for
-        // flagged sources, the fill) stays on the caller's stream, in stream order.
-        hipStream_t hs = pl->overlap ? pl->hub_stream : s;
-        e = launch_hub_plan(pl, pl->d_args, hs);
-        if (e == hipSuccess && pl->overlap) {
-            if (hipEventRecord(pl->slots[pl->slot].ev_hub, hs) != hipSuccess ||
-                hipStreamWaitEvent(s, pl->slots[pl->slot].ev_hub, 0) != hipSuccess)
-                e = hipErrorUnknown;
-        }
-        if (e == hipSuccess && !pl->fb_none)
-            e = launch_solve(pl->d_args_fb, pl->grid_in_lds, pl->algo, pl->ka.p.NS, pl->ka.p.V, pl->fb_blocks, s);
-        hipEvent_t f0 = nullptr;
-        if (e == hipSuccess && hipEventCreate(&f0) == hipSuccess) (void)hipEventRecord(f0, s);
-        if (e == hipSuccess) e = launch_fill(pl->d_args_fill, pl->ka.p.perm, gx, gy, s);
-        // the slot's tables are free again once this fill has read them
-        if (e == hipSuccess && pl->overlap && hipEventRecord(pl->slots[pl->slot].ev_fill, s) != hipSuccess)
-            e = hipErrorUnknown;
-        pl->timed_fill.push_back({f0, nullptr, false});  // one per pass (f0 may be null), as in `timed`
-    } else if (pl->hp.hub) {
-        // closed-form hub solve: the lane kernel for the sources with few queries, the
-        // hub kernel for the others, then the SSSP kernel for the sources they flagged
-        // (usually none; those workgroups exit at once).  Once a pass of this plan (same
-        // inputs, deterministic result) had no fallback source, the hub launches end the
-        // pass on their own.
-        // (a Fleetfoot lane plan relaunches hub_kernel for the sources its lane kernel
-        // relisted, until a pass had none)
-        const bool big = pl->ka.nsrc > pl->n_lane || (pl->d_relist && !pl->fb_none);
-        e = hipSuccess;
-        if (pl->n_lane) {
-            const KArgs *la = pl->fb_none && !big ? pl->d_args_lane_last : pl->d_args_lane;
-            // (a plan whose memo gate held: the destinations only, from the grid's rows)
-            if (pl->lane_g)
-                e = launch_hub_group(la, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->n_lane, pl->lane_g, pl->hp.nonlin, s);
-            else if (pl->ka.lane_memo)
-                e = launch_hub_lane_memo(la, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->n_lane, s);
-            else
-                e = launch_hub_lane(la, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->n_lane, pl->hp.nonlin, s);
-        }
-        if (e == hipSuccess && big) e = launch_hub_plan(pl, pl->fb_none ? pl->d_args_hub_last : pl->d_args, s);
-        // certified fallback: the slots given to the staged sources in source order,
-        // their closed forms, the check, one repair sweep, the check again (each exits at
-        // once without slots); the SSSP launch then
-        // emits every certified source from its slot and solves the rest
-        if (e == hipSuccess && !pl->fb_none && pl->cert_cap) {
-            e = launch_cert_select(pl->d_args, s);
-            if (e == hipSuccess) e = launch_fill(pl->d_args_cert, pl->ka.p.perm, pl->cert_fill_gx, 1, s);
-            // (MR_CERT_NOSWEEP=1: diagnostics, the first check's state stays for MR_CERT_DEBUG)
-            static const bool nosweep = std::getenv("MR_CERT_NOSWEEP") != nullptr;
-            // the first check marks its failing cells: the sweep's seeds
-            if (e == hipSuccess) e = launch_cert_check(pl->d_args, pl->cert_check_gx, pl->cert_cap, nosweep ? 0u : 1u, s);
-            if (!nosweep) {
-                // the repair: each slot's window, the tile sweep (Legs / Time first), the
-                // round-5 sweep for the others
-                if (e == hipSuccess) e = launch_cert_window(pl->d_args, pl->cert_cap, s);
-                if (e == hipSuccess && pl->cert_tile_wgs) e = launch_cert_tile(pl->d_args, pl->cert_tile_wgs, s);
-                if (e == hipSuccess) e = launch_cert_sweep(pl->d_args, pl->cert_cap, s);
-                if (e == hipSuccess) e = launch_cert_check(pl->d_args, pl->cert_check_gx, pl->cert_cap, 0u, s);
-                // further rounds for the slots whose last check still failed: the closed form
-                // again after a promotion, else the sweep again from the repaired words
-                for (int round = 0; round < kCertRounds && e == hipSuccess && pl->d_args_r2; ++round) {
-                    e = launch_cert_promote(pl->d_args, pl->cert_cap, pl->d_cert_redo, s);
-                    if (e == hipSuccess) e = launch_fill(pl->d_args_cert_r2, pl->ka.p.perm, pl->cert_fill_gx, 1, s);
-                    if (e == hipSuccess) e = launch_cert_check(pl->d_args_r2, pl->cert_check_gx, pl->cert_cap, 1u, s);
-                    if (e == hipSuccess) e = launch_cert_window(pl->d_args_r2, pl->cert_cap, s);
-                    if (e == hipSuccess && pl->cert_tile_wgs) e = launch_cert_tile(pl->d_args_r2, pl->cert_tile_wgs, s);
-                    if (e == hipSuccess) e = launch_cert_sweep(pl->d_args_r2, pl->cert_cap, s);
-                    if (e == hipSuccess) e = launch_cert_check(pl->d_args_r2, pl->cert_check_gx, pl->cert_cap, 0u, s);
-                }
-            }
-        }
-        if (e == hipSuccess && !pl->fb_none)
-            e = launch_solve(pl->d_args_fb, pl->grid_in_lds, pl->algo, pl->ka.p.NS, pl->ka.p.V, pl->fb_blocks, s);
-    } else {
-        e = launch_solve(pl->d_args, pl->grid_in_lds, pl->algo, pl->ka.p.NS, pl->ka.p.V, pl->blocks, s);
-    }
+    hipError_t e;
+    if (all_hub && pl->fused) e = run_fused(pl, prev_slot, s);
+    else if (all_hub) e = run_all(pl, s);
+    else if (pl->hp.hub) e = run_hub(pl, s);
+    else e = launch_solve(pl->cur().args.get(), pl->grid_in_lds, pl->algo, pl->ka.p.NS, pl->ka.p.V, pl->blocks, s);
     // raw outputs for a collective: the overflow pool in record order (byte-deterministic)
-    if (e == hipSuccess && pl->ovf_order && !pl->all_mode) e = launch_ovf_order(pl->d_args, nrec_of(pl->hp), pl->d_ovf_tmp, s);
-    (void)hipEventRecord(e1, s);
+    if (e == hipSuccess && pl->out.ovf_order && !pl->all_mode)
+        e = launch_ovf_order(pl->cur().args.get(), nrec_of(pl->hp), pl->out.ovf_tmp.get(), s);
+    (void)hipEventRecord(e1.get(), s);
     // the pass's end event doubles as the plan's last event (plan_sync): a record of
-    // its own cost ~6 us of command-processor time per pass
-    if (pl->ev_last_orphan) (void)hipEventDestroy(pl->ev_last);
-    pl->ev_last = e1;
-    pl->ev_last_orphan = false;
+    // its own cost ~6 us of command-processor time per pass.  `timed` owns it from here.
+    pl->ev_last_keep = Event();
+    pl->ev_last = e1.get();
     pl->last_stream = s;
-    pl->timed.push_back({e0, e1});
-    if (!pl->timed_fill.empty() && !pl->timed_fill.back().second) pl->timed_fill.back().second = e1;
+    if (!pl->timed_fill.empty() && !pl->timed_fill.back().second) pl->timed_fill.back().second = e1.get();
+    pl->timed.push_back({std::move(e0), std::move(e1)});
     if (e != hipSuccess) return fail(MR_ERR_DEVICE, std::string("launch: ") + hipGetErrorString(e));
     return MR_OK;
 }
@@ -3053,14 +2823,15 @@ extern "C" int mr_plan_run(mr_plan *pl, void *stream) {
 static bool plan_sync(mr_plan *pl) {
     bool ok = true;
     if (pl->runs && pl->ev_last) ok = hipEventSynchronize(pl->ev_last) == hipSuccess;
-    if (pl->stream) ok = hipStreamSynchronize(pl->stream) == hipSuccess && ok;
-    if (pl->hub_stream) ok = hipStreamSynchronize(pl->hub_stream) == hipSuccess && ok;
+    if (pl->stream) ok = hipStreamSynchronize(pl->stream.get()) == hipSuccess && ok;
+    if (pl->hub_stream) ok = hipStreamSynchronize(pl->hub_stream.get()) == hipSuccess && ok;
     return ok;
 }
 
-// counters after the plan's passes have drained; notes a pass without fallback sources
+// the counters of the latest pass's slot after the plan's passes have drained; notes a
+// pass without fallback sources
 static int read_counters(mr_plan *pl, uint32_t ctr[kCtrWords]) {
-    if (!plan_sync(pl) || hipMemcpy(ctr, pl->d_counter, kCtrWords * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    if (!plan_sync(pl) || hipMemcpy(ctr, pl->cur().counter.get(), kCtrWords * 4, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(MR_ERR_DEVICE, "copy counter");
     if (pl->hp.hub && pl->runs && !pl->ka.fb_all && ctr[kCtrLastFb] == 0 && ctr[kCtrLastRelist] == 0) pl->fb_none = true;
     return MR_OK;
@@ -3068,33 +2839,33 @@ static int read_counters(mr_plan *pl, uint32_t ctr[kCtrWords]) {
 
 // Folds the pending event pairs into the plan's running totals, all but the newest
 // `keep` of them (waits for those passes; the fill pairs share their end event
-// with the pass pairs, which destroy it).
+// with the pass pairs, which own it), and destroys their events by erasing them.
 static void fold_timed(mr_plan *pl, size_t keep) {
     const size_t nf = pl->timed_fill.size() > keep ? pl->timed_fill.size() - keep : 0;
     for (size_t i = 0; i < nf; ++i) {
         auto &f = pl->timed_fill[i];
         float ms = 0.f;
         // all-destinations plans push one pair to each list per pass: the lists align
-        const hipEvent_t f0 = f.whole && pl->timed.size() == pl->timed_fill.size() ? pl->timed[i].first : f.first;
+        const hipEvent_t f0 =
+            f.whole && pl->timed.size() == pl->timed_fill.size() ? pl->timed[i].first.get() : f.first.get();
         if (f0 && f.second && hipEventSynchronize(f.second) == hipSuccess &&
             hipEventElapsedTime(&ms, f0, f.second) == hipSuccess) {
             pl->acc_fill_ms += ms;
             ++pl->acc_fill_n;
         }
-        if (f.first) (void)hipEventDestroy(f.first);
     }
     pl->timed_fill.erase(pl->timed_fill.begin(), pl->timed_fill.begin() + ptrdiff_t(nf));
     const size_t n = pl->timed.size() > keep ? pl->timed.size() - keep : 0;
     for (size_t i = 0; i < n; ++i) {
         auto &e = pl->timed[i];
         float ms = 0.f;
-        if (hipEventSynchronize(e.second) == hipSuccess && hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) {
+        if (hipEventSynchronize(e.second.get()) == hipSuccess &&
+            hipEventElapsedTime(&ms, e.first.get(), e.second.get()) == hipSuccess) {
             pl->acc_ms += ms;
             ++pl->acc_n;
         }
-        (void)hipEventDestroy(e.first);
-        if (e.second == pl->ev_last) pl->ev_last_orphan = true;  // plan_sync still waits on it
-        else (void)hipEventDestroy(e.second);
+        // plan_sync still waits on the last pass's end event: the plan keeps that one
+        if (e.second.get() == pl->ev_last) pl->ev_last_keep = std::move(e.second);
     }
     pl->timed.erase(pl->timed.begin(), pl->timed.begin() + ptrdiff_t(n));
 }
@@ -3126,14 +2897,12 @@ extern "C" int mr_plan_bind_outputs_ex(mr_plan *pl, void *d_results, void *d_com
     pl->ka.out_cmd = reinterpret_cast<OutCmd *>(d_commands);
     if (d_overflow && overflow_cap) {  // overflow_cap 0 keeps the plan's own pool
         // the pool in record order after every pass (ovf_order_kernel): its staging buffer
-        pfree(pl->d_ovf_tmp);
-        pl->d_ovf_tmp = nullptr;
-        pl->ovf_order = false;
-        if (pmalloc(reinterpret_cast<void **>(&pl->d_ovf_tmp), size_t(overflow_cap) * sizeof(OutCmd)) != hipSuccess)
-            return fail(MR_ERR_DEVICE, "bind_outputs: overflow staging");
+        // (alloc gives back the staging block of an earlier binding first)
+        pl->out.ovf_order = false;
+        if (pl->out.ovf_tmp.alloc(overflow_cap) != hipSuccess) return fail(MR_ERR_DEVICE, "bind_outputs: overflow staging");
         pl->ka.ovf = reinterpret_cast<OutCmd *>(d_overflow);
         pl->ka.ovf_cap = overflow_cap;
-        pl->ovf_order = true;
+        pl->out.ovf_order = true;
     }
     if (upload_args(pl) != MR_OK) return fail(MR_ERR_DEVICE, "kernel args");
     return MR_OK;
@@ -3162,9 +2931,9 @@ static int handed_over(mr_plan *pl, std::vector<uint32_t> &fb) {
     if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");
     uint32_t ctr[kCtrWords];
     if (int st = read_counters(pl, ctr)) return st;
-    const uint32_t nf = pl->hp.hub && pl->d_fb ? std::min(ctr[kCtrLastFb], pl->ka.nsrc) : 0u;
+    const uint32_t nf = pl->hp.hub && pl->cur().fb.get() ? std::min(ctr[kCtrLastFb], pl->ka.nsrc) : 0u;
     fb.resize(nf);
-    if (nf && hipMemcpy(fb.data(), pl->d_fb, size_t(nf) * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    if (nf && hipMemcpy(fb.data(), pl->cur().fb.get(), size_t(nf) * 4, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(MR_ERR_DEVICE, "copy fallback list");
     std::sort(fb.begin(), fb.end(), [](uint32_t a, uint32_t b) { return (a & ~kFbCertified) < (b & ~kFbCertified); });
     if (!fb.empty())
@@ -3203,12 +2972,12 @@ extern "C" int mr_plan_get_stats(mr_plan *pl, mr_plan_stats *out) {
     std::memset(out, 0, sizeof(*out));
     uint32_t ctr[kCtrWords];
     if (int st = read_counters(pl, ctr)) return st;
-    if (std::getenv("MR_CERT_DEBUG") && pl->cert_cap) {  // diagnostics: each slot's last check
-        const size_t parts = pl->cert_check_gx, n = size_t(pl->cert_cap) * parts * kCertSt;
-        std::vector<uint32_t> cs(n), src(pl->cert_cap);
-        if (hipMemcpy(cs.data(), pl->d_cert_st, n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(src.data(), pl->d_cert_src, src.size() * 4, hipMemcpyDeviceToHost) == hipSuccess)
-            for (uint32_t k = 0; k < pl->cert_cap; ++k) {
+    if (std::getenv("MR_CERT_DEBUG") && pl->cert.cap) {  // diagnostics: each slot's last check
+        const size_t parts = pl->cert.check_gx, n = size_t(pl->cert.cap) * parts * kCertSt;
+        std::vector<uint32_t> cs(n), src(pl->cert.cap);
+        if (hipMemcpy(cs.data(), pl->cert.st.get(), n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(src.data(), pl->cert.src.get(), src.size() * 4, hipMemcpyDeviceToHost) == hipSuccess)
+            for (uint32_t k = 0; k < pl->cert.cap; ++k) {
                 uint32_t key = kNone32, fails = 0, x0 = kNone32, x1 = 0, y0 = kNone32, y1 = 0;
                 for (size_t j = 0; j < parts; ++j) {
                     const uint32_t *q = &cs[(k * parts + j) * kCertSt];
@@ -3222,7 +2991,7 @@ extern "C" int mr_plan_get_stats(mr_plan *pl, mr_plan_stats *out) {
                 }
                 const uint32_t v = src[k] < pl->grid->V ? src[k] : 0;
                 uint32_t wn[16] = {0};
-                if (pl->d_cert_win) (void)hipMemcpy(wn, pl->d_cert_win + size_t(k) * kWinWords, sizeof(wn), hipMemcpyDeviceToHost);
+                if (pl->cert.win.get()) (void)hipMemcpy(wn, pl->cert.win.get() + size_t(k) * kWinWords, sizeof(wn), hipMemcpyDeviceToHost);
                 std::fprintf(stderr,
                              "MR_CERT_DEBUG slot %u src (%d,%d): fails %u key %u box x %d..%d y %d..%d | repair mode %u "
                              "tiles %ux%u steps %u fail %u promoted %08x%08x | tile 0: steps %.1f us, %u exchanges %.1f us\n",
@@ -3233,7 +3002,7 @@ extern "C" int mr_plan_get_stats(mr_plan *pl, mr_plan_stats *out) {
                              wn[kWinTXchg] * 0.01);
                 {
                     uint32_t wy[29] = {0};
-                    if (hipMemcpy(wy, pl->d_cert_win + size_t(k) * kWinWords + kWinWhy, sizeof(wy), hipMemcpyDeviceToHost) == hipSuccess)
+                    if (hipMemcpy(wy, pl->cert.win.get() + size_t(k) * kWinWords + kWinWhy, sizeof(wy), hipMemcpyDeviceToHost) == hipSuccess)
                         for (uint32_t f = 0; f < std::min(wy[0], 7u); ++f)
                             std::fprintf(stderr, "MR_CERT_DEBUG   failing cell (%d,%d)%s tests %#x own %u best %u\n",
                                          int(wy[1 + 4 * f] & 0xFFFFu) - int(pl->grid->H), int(wy[1 + 4 * f] >> 16) - int(pl->grid->H),
@@ -3242,7 +3011,7 @@ extern "C" int mr_plan_get_stats(mr_plan *pl, mr_plan_stats *out) {
                 if (wn[kWinMode] == kWinTile) {  // the tiles' step / exchange times and settles
                     const uint32_t nt = std::min(wn[kWinNtx] * wn[kWinNty], kTileMaxTiles);
                     std::vector<uint32_t> ts(size_t(nt) * 4);
-                    if (hipMemcpy(ts.data(), pl->d_cert_win + size_t(k) * kWinWords + kWinStat, ts.size() * 4,
+                    if (hipMemcpy(ts.data(), pl->cert.win.get() + size_t(k) * kWinWords + kWinStat, ts.size() * 4,
                                   hipMemcpyDeviceToHost) == hipSuccess)
                         for (uint32_t t = 0; t < nt; ++t)
                             std::fprintf(stderr, "MR_CERT_DEBUG   tile %u: steps %u in %.1f us, exchanges %.1f us (publish %.1f, wait %.1f)\n", t,
@@ -3258,12 +3027,12 @@ extern "C" int mr_plan_get_stats(mr_plan *pl, mr_plan_stats *out) {
     out->fallback_sources = pl->hp.hub ? ctr[kCtrLastFb] : 0u;
     out->num_specials = pl->ka.p.NS;
     out->num_regions = pl->hp.nreg;
-    out->hub_workgroups = pl->hub_blocks;
+    out->hub_workgroups = pl->hub.hub_blocks;
     out->sssp_workgroups = pl->blocks;
     out->specials_per_lane = !pl->hp.hub ? 0u : (pl->hp.wide ? hub_wide_spl(pl->ka.p.NS) : 1u);
     out->region_boundary_cells = pl->hp.wide && pl->hp.rb_off && !pl->hp.rb_off->empty() ? pl->hp.rb_off->back() : 0u;
-    out->lane_sources = pl->lane_g ? 0u : pl->n_lane;
-    out->lanes_per_source = !pl->n_lane ? 0u : (pl->lane_g ? pl->lane_g : 1u);
+    out->lane_sources = pl->hub.lane_g ? 0u : pl->hub.n_lane;
+    out->lanes_per_source = !pl->hub.n_lane ? 0u : (pl->hub.lane_g ? pl->hub.lane_g : 1u);
     out->certified_sources = ctr[kCtrLastCert];
     out->fill_launch = !(pl->hp.hub && pl->all_mode) ? MR_FILL_NONE
                        : pl->fused                   ? MR_FILL_FUSED
@@ -3391,25 +3160,25 @@ static int check_device_errors(mr_plan *pl, uint32_t &flags, uint32_t *ctr_out =
     if (int st = read_counters(pl, ctr)) return st;
     if (ctr_out) std::memcpy(ctr_out, ctr, sizeof(ctr));  // (read before the flags are collected)
     flags = ctr[kCtrFlags];
-    if (flags) (void)hipMemset(pl->d_counter + kCtrFlags, 0, 4);  // collected
+    if (flags) (void)hipMemset(pl->cur().counter.get() + kCtrFlags, 0, 4);  // collected
     // overlap plans: the other slots' counter blocks belong to earlier passes; their
     // flags and written counts are checked (and collected) as well
     for (uint32_t i = 0; i < pl->slots.size(); ++i) {
         const mr_plan::Slot &k = pl->slots[i];
-        if (i == pl->slot || !k.counter) continue;
+        if (i == pl->slot) continue;
         uint32_t oc[kCtrWords];
-        if (hipMemcpy(oc, k.counter, kCtrWords * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(oc, k.counter.get(), kCtrWords * 4, hipMemcpyDeviceToHost) != hipSuccess)
             return fail(MR_ERR_DEVICE, "copy counter");
-        if (oc[kCtrFlags]) (void)hipMemset(k.counter + kCtrFlags, 0, 4);
+        if (oc[kCtrFlags]) (void)hipMemset(k.counter.get() + kCtrFlags, 0, 4);
         flags |= oc[kCtrFlags];  // a fused plan's look-ahead solve may have flagged a slot not yet filled
         if (flags == 0 && k.used && oc[kCtrLastWritten] != nrec_of(pl->hp))
             return fail(MR_ERR_DEVICE, "internal: " + std::to_string(oc[kCtrLastWritten]) + " of " +
                                            std::to_string(nrec_of(pl->hp)) + " records written (an earlier pass)");
     }
 #ifdef MR_HUBDUMP
-    if (pl->d_dbg) {
+    if (pl->out.dbg.get()) {
         std::vector<uint32_t> d(64 * 16);
-        (void)hipMemcpy(d.data(), pl->d_dbg, d.size() * 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(d.data(), pl->out.dbg.get(), d.size() * 4, hipMemcpyDeviceToHost);
         for (uint32_t t = 0; t <= pl->ka.p.NS; ++t) {
             const uint32_t *r = &d[t * 16];
             const uint32_t v = t ? pl->hp.sp[t].v : pl->ka.dbg_blocks;
@@ -3427,10 +3196,10 @@ static int check_device_errors(mr_plan *pl, uint32_t &flags, uint32_t *ctr_out =
 #endif
     if (std::getenv("MR_DEBUG")) {
         std::fprintf(stderr, "MR_DEBUG hub=%d sources=%u fallback=%u flags=%u hub_blocks=%u\n", int(pl->hp.hub),
-                     pl->ka.nsrc, ctr[kCtrLastFb], ctr[kCtrFlags], pl->hub_blocks);
-        if (pl->d_fb && ctr[kCtrLastFb] <= pl->ka.nsrc && host_arrays(pl) == MR_OK) {
+                     pl->ka.nsrc, ctr[kCtrLastFb], ctr[kCtrFlags], pl->hub.hub_blocks);
+        if (pl->cur().fb.get() && ctr[kCtrLastFb] <= pl->ka.nsrc && host_arrays(pl) == MR_OK) {
             std::vector<uint32_t> fb(ctr[kCtrLastFb]);
-            (void)hipMemcpy(fb.data(), pl->d_fb, fb.size() * 4, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(fb.data(), pl->cur().fb.get(), fb.size() * 4, hipMemcpyDeviceToHost);
             std::fprintf(stderr, "MR_DEBUG fallback sources (vertex):");
             for (uint32_t s : fb) std::fprintf(stderr, " %u%s", pl->hp.src_v[s & ~kFbCertified], (s & kFbCertified) ? "c" : "");
             std::fprintf(stderr, "\n");
@@ -3484,16 +3253,9 @@ static const mr_cell_index *grid_idx_rank(const mr_grid *g, int dev) {
     if (!g->d_idx_rank) {
         std::vector<mr_cell_index> t(g->V);
         for (uint32_t r = 0; r < g->V; ++r) t[r] = g->idx[g->rank_inv[r]];
-        mr_cell_index *d = nullptr;
-        if (dev_malloc(reinterpret_cast<void **>(&d), std::max<size_t>(t.size(), 1) * sizeof(mr_cell_index)) != hipSuccess)
-            return nullptr;
-        if (!t.empty() && hipMemcpy(d, t.data(), t.size() * sizeof(mr_cell_index), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return nullptr;
-        }
-        g->d_idx_rank = d;
+        if (upload(g->d_idx_rank, t, DevMem::direct) != hipSuccess) return nullptr;
     }
-    return g->d_idx_rank;
+    return g->d_idx_rank.get();
 }
 
 // mr_plan_fetch with the records expanded on the device (mr_k_decode.hip) into the ABI
@@ -3503,8 +3265,7 @@ static const mr_cell_index *grid_idx_rank(const mr_grid *g, int dev) {
 static bool plan_fetch_device(mr_plan *pl, mr_result *results, mr_command *pool, uint64_t pool_cap, int &ret) {
     const HostPlan &hp = pl->hp;
     const uint32_t nq = hp.nq, nrec = nrec_of(hp), mc = hp.p.max_cmds;
-    if (const char *e = std::getenv("MR_HOST_DECODE"))
-        if (!std::strcmp(e, "1")) return false;
+    if (env_host_decode()) return false;
     if (!pool || !nq || pl->all_mode) return false;
     const mr_cell_index *idx_rank = grid_idx_rank(pl->grid, pl->device);
     if (!idx_rank) return false;
@@ -3516,28 +3277,27 @@ static bool plan_fetch_device(mr_plan *pl, mr_result *results, mr_command *pool,
     const CmdScale cs = cmd_scale(hp);
     size_t temp_bytes = 0;
     (void)decode_records_device(nullptr, nullptr, nullptr, 0, nullptr, 0, nq, mc, nullptr, 0, 0, 0, 0, 0, 0, nullptr,
-                                nullptr, nullptr, &temp_bytes, nullptr, nullptr, 0, nullptr, pl->stream);
-    void *scratch = nullptr, *d_out = nullptr, *d_pool = nullptr;
+                                nullptr, nullptr, &temp_bytes, nullptr, nullptr, 0, nullptr, pl->stream.get());
+    DevBuf<char> scratch_buf;
+    DevBuf<mr_result> out_buf;
+    DevBuf<mr_command> pool_buf;
     const size_t cnt_b = (size_t(nq) * 4 + 255) / 256 * 256, tail = 256;
-    if (pmalloc(&scratch, 2 * cnt_b + temp_bytes + tail) != hipSuccess ||
-        pmalloc(&d_out, size_t(nq) * sizeof(mr_result)) != hipSuccess ||
-        pmalloc(&d_pool, size_t(pcap) * sizeof(mr_command)) != hipSuccess) {
-        pfree(scratch);
-        pfree(d_out);
+    if (scratch_buf.alloc(2 * cnt_b + temp_bytes + tail) != hipSuccess || out_buf.alloc(nq) != hipSuccess ||
+        pool_buf.alloc(pcap) != hipSuccess)
         return false;  // the host decoder needs no device memory
-    }
+    void *const scratch = scratch_buf.get(), *const d_out = out_buf.get(), *const d_pool = pool_buf.get();
     uint32_t *cnt = static_cast<uint32_t *>(scratch), *off = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + cnt_b);
     uint32_t *err = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + 2 * cnt_b);
     void *temp = static_cast<char *>(scratch) + 2 * cnt_b + tail;
-    hipError_t e = decode_records_device(pl->ka.out_res, pl->ka.out_cmd, pl->ka.ovf, nov, pl->d_qi, nrec, nq, mc, idx_rank,
+    hipError_t e = decode_records_device(pl->ka.out_res, pl->ka.out_cmd, pl->ka.ovf, nov, pl->batch.qi, nrec, nq, mc, idx_rank,
                                          pl->grid->V, cs.rgt, cs.soe, cs.shq, cs.sfm, cs.ff, cnt, off, temp, &temp_bytes,
                                          static_cast<mr_result *>(d_out), static_cast<mr_command *>(d_pool), pcap, err,
-                                         pl->stream);
+                                         pl->stream.get());
     uint32_t tailw[3] = {0, 0, 0};  // err, off and count of the last query: the commands written
-    if (e == hipSuccess) e = hipMemcpyAsync(&tailw[0], err, 4, hipMemcpyDeviceToHost, pl->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&tailw[1], off + (nq - 1), 4, hipMemcpyDeviceToHost, pl->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&tailw[2], cnt + (nq - 1), 4, hipMemcpyDeviceToHost, pl->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(pl->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&tailw[0], err, 4, hipMemcpyDeviceToHost, pl->stream.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(&tailw[1], off + (nq - 1), 4, hipMemcpyDeviceToHost, pl->stream.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(&tailw[2], cnt + (nq - 1), 4, hipMemcpyDeviceToHost, pl->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(pl->stream.get());
     // every command fits the caller's pool (offsets are the prefix of the counts): results
     // and commands in one pipelined copy, else the results first, to find the cut
     const uint64_t total = uint64_t(tailw[1]) + tailw[2];
@@ -3545,7 +3305,7 @@ static bool plan_fetch_device(mr_plan *pl, mr_result *results, mr_command *pool,
     if (e == hipSuccess) {
         const D2HSeg sg[2] = {{results, d_out, size_t(nq) * sizeof(mr_result)},
                               {pool, d_pool, fits ? size_t(total) * sizeof(mr_command) : 0}};
-        e = copy_d2h(sg, 2, pl->stream);
+        e = copy_d2h(sg, 2, pl->stream.get());
     }
     // queries without a record (an invalid index), and the status to return: the first
     // error in query order, or MR_ERR_CAPACITY once a label's commands do not fit the
@@ -3598,14 +3358,12 @@ static bool plan_fetch_device(mr_plan *pl, mr_result *results, mr_command *pool,
     const uint64_t ncopy = std::min<uint64_t>(end, pcap);
     if (e == hipSuccess && !fits && ncopy && !(tailw[0] & 1u)) {
         const D2HSeg sg{pool, d_pool, size_t(ncopy) * sizeof(mr_command)};
-        e = copy_d2h(&sg, 1, pl->stream);
+        e = copy_d2h(&sg, 1, pl->stream.get());
     }
-    // the blocks go back to the cache, which hands them out with no implicit sync: on
-    // every path (a failed enqueue included) the work queued on them must be done first
-    (void)hipStreamSynchronize(pl->stream);
-    pfree(scratch);
-    pfree(d_out);
-    pfree(d_pool);
+    // the blocks go back to the cache on return, and the cache hands them out with no
+    // implicit sync: on every path (a failed enqueue included) the work queued on them
+    // must be done first
+    (void)hipStreamSynchronize(pl->stream.get());
     const double tm1 = timing_on() ? now_ms() : 0.0;
     if (e != hipSuccess) return (ret = fail(MR_ERR_DEVICE, std::string("device fetch: ") + hipGetErrorString(e))), true;
     if (tailw[0] & 1u) return (ret = fail(MR_ERR_DEVICE, "malformed record (overflow tag or cell rank)")), true;
@@ -3719,12 +3477,12 @@ extern "C" int mr_plan_wire_records(mr_plan *pl, void *d_rows, void *d_pool, uin
     if (!pl || (pl->hp.nq && !d_rows) || (pool_cap && !d_pool)) return fail(MR_ERR_INVALID_ARG, "null argument");
     if (pl->all_mode) return fail(MR_ERR_INVALID_ARG, "wire_records: not a query plan");
     if (pl->grid->V > kWireRankMask + 1u) return fail(MR_ERR_INVALID_ARG, "wire_records: grid too large for wire records");
-    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : pl->stream;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : pl->stream.get();
     // ordered after the plan's last pass, whichever stream that ran on
     if (pl->ev_last && pl->last_stream != s && hipStreamWaitEvent(s, pl->ev_last, 0) != hipSuccess)
         return fail(MR_ERR_DEVICE, "wait for the last pass");
     const uint32_t nq = pl->hp.nq, nrec = pl->runs ? nrec_of(pl->hp) : 0u;
-    if (launch_wire(pl->ka.out_res, pl->ka.out_cmd, pl->ka.ovf, pl->d_counter + kCtrLastOvf, pl->ka.ovf_cap, nrec, nq,
+    if (launch_wire(pl->ka.out_res, pl->ka.out_cmd, pl->ka.ovf, pl->cur().counter.get() + kCtrLastOvf, pl->ka.ovf_cap, nrec, nq,
                     pl->hp.p.max_cmds, nullptr, static_cast<uint32_t *>(d_rows), static_cast<uint32_t *>(d_pool), pool_cap,
                     s) !=
         hipSuccess)
@@ -3732,15 +3490,13 @@ extern "C" int mr_plan_wire_records(mr_plan *pl, void *d_rows, void *d_pool, uin
     // on a stream of its own (overlapping the next plan's pass), the encoding reads the
     // plan's outputs after the pass: the plan's next pass waits for it as for a pass
     if (pl->ev_last && pl->last_stream != s) {
-        hipEvent_t ev = nullptr;
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, s) != hipSuccess) {
-            if (ev) (void)hipEventDestroy(ev);
+        Event ev;
+        if (ev.create(hipEventDisableTiming) != hipSuccess || hipEventRecord(ev.get(), s) != hipSuccess) {
             (void)hipStreamSynchronize(s);  // (ordered the slow way)
             return MR_OK;
         }
-        if (pl->ev_last_orphan) (void)hipEventDestroy(pl->ev_last);
-        pl->ev_last = ev;
-        pl->ev_last_orphan = true;
+        pl->ev_last = ev.get();
+        pl->ev_last_keep = std::move(ev);  // (no pass pair holds this one; an event kept before goes)
         pl->last_stream = s;
     }
     return MR_OK;
@@ -3943,10 +3699,9 @@ static bool plan_fetch_wire(mr_plan *pl, mr_result *results, mr_command *pool, u
     // (plan_fetch_device: no host threads, direct DMA into page-locked arrays) stays the
     // default
     const char *fw = std::getenv("MR_FETCH_WIRE");
-    if (!(fw && !std::strcmp(fw, "1")) || !pool || !nq || pl->all_mode || pl->grid->V > kWireRankMask + 1u || !pl->d_qi)
+    if (!(fw && !std::strcmp(fw, "1")) || !pool || !nq || pl->all_mode || pl->grid->V > kWireRankMask + 1u || !pl->batch.qi)
         return false;
-    if (const char *e = std::getenv("MR_HOST_DECODE"))
-        if (!std::strcmp(e, "1")) return false;
+    if (env_host_decode()) return false;
     const double tm0 = timing_on() ? now_ms() : 0.0;
     uint32_t flags = 0, ctr[kCtrWords];
     if ((ret = check_device_errors(pl, flags, ctr)) != MR_OK) return true;  // (syncs the plan)
@@ -3954,36 +3709,33 @@ static bool plan_fetch_wire(mr_plan *pl, mr_result *results, mr_command *pool, u
     const size_t rows_b = size_t(nq) * rw * 4, pool_b = size_t(nov) * 8, cnt_b = (size_t(nq) * 4 + 255) / 256 * 256;
     size_t temp_b = 0;
     (void)wire_fetch_device(nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nq, mc, nullptr, nullptr, nullptr, &temp_b,
-                            nullptr, nullptr, 0, pl->stream);
+                            nullptr, nullptr, 0, pl->stream.get());
     const size_t rows_at = 2 * cnt_b + (temp_b + 255) / 256 * 256;
-    void *d_wire = nullptr;
-    if (pmalloc(&d_wire, rows_at + rows_b + pool_b + 8) != hipSuccess) return false;
-    char *dw = static_cast<char *>(d_wire);
+    DevBuf<char> d_wire;
+    if (d_wire.alloc(rows_at + rows_b + pool_b + 8) != hipSuccess) return false;
+    char *dw = d_wire.get();
     uint32_t *d_cnt = reinterpret_cast<uint32_t *>(dw), *d_off = reinterpret_cast<uint32_t *>(dw + cnt_b);
     uint32_t *d_rows = reinterpret_cast<uint32_t *>(dw + rows_at), *d_pool = d_rows + size_t(nq) * rw;
     PinnedStage &stg = stage_down();
     std::lock_guard<std::mutex> lk(stg.mu);
     char *h = static_cast<char *>(stg.get(rows_b + pool_b + 8));
-    if (!h) {
-        pfree(d_wire);
-        return false;
-    }
+    if (!h) return false;
     const uint32_t *h_rows = reinterpret_cast<const uint32_t *>(h), *h_pool = h_rows + size_t(nq) * rw;
     // chunks of rows copied one after the other, the pool first (the rows of any chunk may
     // point into it); each host part decodes its share of a chunk once that has landed
     // (one chunk: the caller waits for the copies, then the pool decodes; the pool's threads
     // waiting on per-chunk events spun through the process's CPU share on busy hosts)
     const uint32_t nch = 1u;
-    std::vector<hipEvent_t> ev(nch, nullptr);
-    hipError_t e = wire_fetch_device(pl->ka.out_res, pl->ka.out_cmd, pl->ka.ovf, pl->d_counter + kCtrLastOvf, pl->ka.ovf_cap,
-                                     pl->d_qi, nrec, nq, mc, d_cnt, d_off, dw + 2 * cnt_b, &temp_b, d_rows, d_pool, nov,
-                                     pl->stream);
-    if (e == hipSuccess && pool_b) e = hipMemcpyAsync(h + rows_b, d_pool, pool_b, hipMemcpyDeviceToHost, pl->stream);
+    std::vector<Event> ev(nch);
+    hipError_t e = wire_fetch_device(pl->ka.out_res, pl->ka.out_cmd, pl->ka.ovf, pl->cur().counter.get() + kCtrLastOvf, pl->ka.ovf_cap,
+                                     pl->batch.qi, nrec, nq, mc, d_cnt, d_off, dw + 2 * cnt_b, &temp_b, d_rows, d_pool, nov,
+                                     pl->stream.get());
+    if (e == hipSuccess && pool_b) e = hipMemcpyAsync(h + rows_b, d_pool, pool_b, hipMemcpyDeviceToHost, pl->stream.get());
     for (uint32_t c = 0; c < nch && e == hipSuccess; ++c) {
         const size_t lo = size_t(chunk_lo(nq, nch, c)) * rw * 4, hi = size_t(chunk_lo(nq, nch, c + 1)) * rw * 4;
-        e = hipMemcpyAsync(h + lo, reinterpret_cast<char *>(d_rows) + lo, hi - lo, hipMemcpyDeviceToHost, pl->stream);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[c], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventRecord(ev[c], pl->stream);
+        e = hipMemcpyAsync(h + lo, reinterpret_cast<char *>(d_rows) + lo, hi - lo, hipMemcpyDeviceToHost, pl->stream.get());
+        if (e == hipSuccess) e = ev[c].create(hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(ev[c].get(), pl->stream.get());
     }
     const double tm1 = timing_on() ? now_ms() : 0.0;
     HostPool &hpool = HostPool::get();
@@ -3993,7 +3745,7 @@ static bool plan_fetch_wire(mr_plan *pl, mr_result *results, mr_command *pool, u
     const mr_cell_index *cell = idx_of_rank(pl->grid);
     const uint32_t V = pl->grid->V;
     const uint32_t parts = nq >= 65536u ? hpool.size() : 1u;
-    if (e == hipSuccess) e = hipEventSynchronize(ev[nch - 1]);
+    if (e == hipSuccess) e = hipEventSynchronize(ev[nch - 1].get());
     // per (chunk, part): the first error status in its queries, or MR_ERR_CAPACITY
     std::vector<int32_t> p_ret(size_t(nch) * parts, MR_OK), p_err(parts, MR_OK);
     std::vector<const char *> p_msg(parts, nullptr);
@@ -4001,7 +3753,7 @@ static bool plan_fetch_wire(mr_plan *pl, mr_result *results, mr_command *pool, u
     if (e == hipSuccess)
         hpool.run(parts, [&](uint32_t pt) {
             for (uint32_t c = 0; c < nch; ++c) {
-                if (hipError_t x = hipEventSynchronize(ev[c])) {
+                if (hipError_t x = hipEventSynchronize(ev[c].get())) {
                     p_e[pt] = x;
                     break;
                 }
@@ -4058,11 +3810,9 @@ static bool plan_fetch_wire(mr_plan *pl, mr_result *results, mr_command *pool, u
         if (x == MR_ERR_CAPACITY) ret = MR_ERR_CAPACITY;
         else if (ret == MR_OK) ret = x;
     }
-    // the device block goes back to the cache, which hands it out with no implicit sync
-    (void)hipStreamSynchronize(pl->stream);
-    for (hipEvent_t x : ev)
-        if (x) (void)hipEventDestroy(x);
-    pfree(d_wire);
+    // the device block goes back to the cache on return, and the cache hands it out with
+    // no implicit sync
+    (void)hipStreamSynchronize(pl->stream.get());
     if (e != hipSuccess) return (ret = fail(MR_ERR_DEVICE, std::string("wire fetch: ") + hipGetErrorString(e))), true;
     if (err != MR_OK) return (ret = fail(err, msg ? msg : "wire row")), true;
     if (timing_on())
@@ -4073,9 +3823,9 @@ static bool plan_fetch_wire(mr_plan *pl, mr_result *results, mr_command *pool, u
 
 extern "C" void mr_plan_destroy(mr_plan *pl) {
 #ifdef MR_STAMPS
-    if (pl && pl->d_dbg) {  // diagnostic summary: phase cycles summed over workgroups (last launch)
+    if (pl && pl->out.dbg.get()) {  // diagnostic summary: phase cycles summed over workgroups (last launch)
         std::vector<unsigned long long> d(size_t(pl->blocks) * 10 + 16);
-        if (hipMemcpy(d.data(), pl->d_dbg, d.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(d.data(), pl->out.dbg.get(), d.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
             unsigned long long acc[9] = {0};
             for (uint32_t b = 0; b < pl->blocks; ++b)
                 for (int i = 0; i < 9; ++i) acc[i] += d[size_t(b) * 10 + i];
@@ -4177,7 +3927,7 @@ static int sssp_source(mr_plan *pl, uint32_t i, uint32_t &si) {
 static int sssp_table(mr_plan *pl, uint32_t si, std::vector<Rec> &tab) {
     const uint32_t T = pl->ka.p.NS + 1;
     tab.resize(T);
-    if (hipMemcpy(tab.data(), pl->d_tab + size_t(si) * T, T * sizeof(Rec), hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(tab.data(), pl->cur().tab.get() + size_t(si) * T, T * sizeof(Rec), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(MR_ERR_DEVICE, "copy label table");
     return MR_OK;
 }
@@ -4211,7 +3961,7 @@ static bool expand_word(const HostPlan &hp, const std::vector<Rec> &tab, CellWor
 static int copy_source_words(mr_plan *pl, uint32_t si, std::vector<CellWord> &words) {
     const uint32_t S = pl->ka.p.S, pitch = pl->ka.rec_pitch;
     std::vector<CellWord> rows(size_t(S) * pitch);
-    if (hipError_t e = hipMemcpy(rows.data(), pl->d_rec + size_t(si) * S * pitch, rows.size() * sizeof(CellWord),
+    if (hipError_t e = hipMemcpy(rows.data(), pl->out.rec.get() + size_t(si) * S * pitch, rows.size() * sizeof(CellWord),
                                  hipMemcpyDeviceToHost))
         return fail(MR_ERR_DEVICE, std::string("copy records: ") + hipGetErrorString(e));
     words.resize(size_t(S) * S);
@@ -4237,7 +3987,7 @@ extern "C" int mr_sssp_records(mr_plan *pl, uint32_t i, mr_label_record *out) {
 extern "C" int mr_sssp_device_records(mr_plan *pl, void **d_records, uint64_t *bytes) {
     if (!pl || !pl->all_mode) return fail(MR_ERR_INVALID_ARG, "not an all-destinations plan");
     if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // whole records behind the pointer
-    if (d_records) *d_records = pl->d_rec;
+    if (d_records) *d_records = pl->out.rec.get();
     if (bytes) *bytes = uint64_t(pl->ka.nsrc) * pl->ka.p.S * pl->ka.rec_pitch * sizeof(CellWord);
     return MR_OK;
 }
@@ -4252,7 +4002,7 @@ extern "C" int mr_sssp_record_pitch(mr_plan *pl, uint32_t *cells_per_row) {
 extern "C" int mr_sssp_device_tables(mr_plan *pl, void **d_tables, uint64_t *bytes) {
     if (!pl || !pl->all_mode) return fail(MR_ERR_INVALID_ARG, "not an all-destinations plan");
     if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // the latest pass's slot, finished
-    if (d_tables) *d_tables = pl->d_tab;
+    if (d_tables) *d_tables = pl->cur().tab.get();
     if (bytes) *bytes = uint64_t(pl->ka.nsrc) * (pl->ka.p.NS + 1) * sizeof(Rec);
     return MR_OK;
 }
@@ -4315,7 +4065,7 @@ extern "C" int mr_sssp_label(mr_plan *pl, uint32_t i, mr_cell_index dst, mr_resu
     CellWord word;
     std::vector<Rec> tab;
     const size_t at = (size_t(si) * g->S + w / g->S) * pl->ka.rec_pitch + w % g->S;  // padded rows
-    if (hipMemcpy(&word, pl->d_rec + at, sizeof(word), hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(&word, pl->out.rec.get() + at, sizeof(word), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(MR_ERR_DEVICE, "copy label");
     if (int st = sssp_table(pl, si, tab)) return st;
     mr_label_record rec;

@@ -57,6 +57,19 @@ def test_abi_version_and_defaults(eng):
     assert list(p.sort_by) == [abi.SORT_LEGS, abi.SORT_MONEY]
 
 
+def test_cache_live_without_a_device(eng):
+    """mr_cache_live needs no device: with no plan made it reports no blocks (either
+    output may be NULL)."""
+    L = eng.lib()
+    blocks, nbytes = C.c_uint64(99), C.c_uint64(99)
+    L.mr_cache_live(C.byref(blocks), C.byref(nbytes))
+    assert (blocks.value, nbytes.value) == (0, 0)
+    L.mr_cache_live(None, None)
+    L.mr_cache_trim()
+    L.mr_cache_live(C.byref(blocks), None)
+    assert blocks.value == 0
+
+
 def test_grid_validation_on_host(eng):
     m = SyntheticMap(9, campfires_per_homeland=2, seed=1)
     g = eng.MapGrid(m.cells())
