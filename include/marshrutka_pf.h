@@ -257,7 +257,9 @@ int mr_decode_records(const mr_grid *grid, const mr_params *params, const void *
  * the previous one ended, src/pathfinder.rs:223-234).  A label longer than max_cmds has its
  * commands at d_pool (8 B each, pool_cap commands); one that does not fit reads
  * MR_ERR_CAPACITY.  Enqueued on `stream` (null: the plan's) after the plan's last pass;
- * rows and pool are rewritten by the next call.  Needs a grid of at most 2^25 cells.
+ * rows and pool are rewritten by the next call.  Needs a grid of at most 2^25 cells and a
+ * plan of max_cmds <= 63 (the first word keeps the command count in a 7-bit code whose values
+ * from 64 up mean "in the pool" or a status): MR_ERR_INVALID_ARG for a plan with more slots.
  * No reference counterpart (the reference returns labels in process). */
 uint32_t mr_wire_row_bytes(uint32_t max_cmds);
 int mr_plan_wire_records(mr_plan *plan, void *d_rows, void *d_pool, uint32_t pool_cap, void *stream);

@@ -308,6 +308,9 @@ enum : uint32_t { kWinNone = 0, kWinTile = 1, kWinOld = 2, kWinWide = 3 };
 // {kind << 29 | payload, rank of its `to` cell}: a command's `from` is the previous one's
 // `to`, and the metrics are the commands' sums (TotalCost::add_assign recomputes them the
 // same way, src/cost.rs:299-313), so neither crosses the wire.  The pool: 2 words a command.
+// The code has 7 bits, so an in-slot count is at most kWireOvf - 1: plans of max_cmds >=
+// kWireOvf have no wire records (mr_plan_wire_records refuses them, mr_plan_fetch decodes
+// them on the device).
 constexpr uint32_t kWireRankBits = 25, kWireRankMask = (1u << kWireRankBits) - 1u;
 constexpr uint32_t kWireOvf = 64u, kWireStatus = 65u;
 

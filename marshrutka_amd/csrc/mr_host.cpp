@@ -84,8 +84,8 @@ constexpr int kCertRounds = 2;  // certificate rounds after the first (cert_prom
 int cert_tile_occupancy();
 hipError_t launch_ovf_order(const KArgs *d_args, uint32_t nrec, OutCmd *tmp, hipStream_t stream);
 hipError_t launch_wire(const OutResult *res, const OutCmd *slots, const OutCmd *ovf, const uint32_t *nov, uint32_t ovf_cap,
-                       uint32_t nrec, uint32_t nq, uint32_t mc, const uint32_t *q_id, uint32_t *rows, uint32_t *wpool,
-                       uint32_t wpool_cap, hipStream_t stream);
+                       uint32_t nrec, uint32_t nq, uint32_t mc, uint32_t *rows, uint32_t *wpool, uint32_t wpool_cap,
+                       hipStream_t stream);
 hipError_t wire_fetch_device(const OutResult *res, const OutCmd *slots, const OutCmd *ovf, const uint32_t *nov,
                              uint32_t ovf_cap, const uint32_t *q_id, uint32_t nrec, uint32_t nq, uint32_t mc, uint32_t *cnt,
                              uint32_t *off, void *temp, size_t *temp_bytes, uint32_t *rows, uint32_t *wpool,
@@ -3477,15 +3477,17 @@ extern "C" int mr_plan_wire_records(mr_plan *pl, void *d_rows, void *d_pool, uin
     if (!pl || (pl->hp.nq && !d_rows) || (pool_cap && !d_pool)) return fail(MR_ERR_INVALID_ARG, "null argument");
     if (pl->all_mode) return fail(MR_ERR_INVALID_ARG, "wire_records: not a query plan");
     if (pl->grid->V > kWireRankMask + 1u) return fail(MR_ERR_INVALID_ARG, "wire_records: grid too large for wire records");
+    // (the header's 7-bit code: an in-slot command count is below kWireOvf)
+    if (pl->hp.p.max_cmds >= kWireOvf)
+        return fail(MR_ERR_INVALID_ARG, "wire_records: max_cmds " + std::to_string(pl->hp.p.max_cmds) +
+                                            " is above the wire format's limit of " + std::to_string(kWireOvf - 1u));
     hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : pl->stream.get();
     // ordered after the plan's last pass, whichever stream that ran on
     if (pl->ev_last && pl->last_stream != s && hipStreamWaitEvent(s, pl->ev_last, 0) != hipSuccess)
         return fail(MR_ERR_DEVICE, "wait for the last pass");
     const uint32_t nq = pl->hp.nq, nrec = pl->runs ? nrec_of(pl->hp) : 0u;
     if (launch_wire(pl->ka.out_res, pl->ka.out_cmd, pl->ka.ovf, pl->cur().counter.get() + kCtrLastOvf, pl->ka.ovf_cap, nrec, nq,
-                    pl->hp.p.max_cmds, nullptr, static_cast<uint32_t *>(d_rows), static_cast<uint32_t *>(d_pool), pool_cap,
-                    s) !=
-        hipSuccess)
+                    pl->hp.p.max_cmds, static_cast<uint32_t *>(d_rows), static_cast<uint32_t *>(d_pool), pool_cap, s) != hipSuccess)
         return fail(MR_ERR_DEVICE, "wire kernel");
     // on a stream of its own (overlapping the next plan's pass), the encoding reads the
     // plan's outputs after the pass: the plan's next pass waits for it as for a pass
@@ -3701,6 +3703,7 @@ static bool plan_fetch_wire(mr_plan *pl, mr_result *results, mr_command *pool, u
     const char *fw = std::getenv("MR_FETCH_WIRE");
     if (!(fw && !std::strcmp(fw, "1")) || !pool || !nq || pl->all_mode || pl->grid->V > kWireRankMask + 1u || !pl->batch.qi)
         return false;
+    if (mc >= kWireOvf) return false;  // (wire rows carry in-slot counts below kWireOvf: the device decoder fetches)
     if (env_host_decode()) return false;
     const double tm0 = timing_on() ? now_ms() : 0.0;
     uint32_t flags = 0, ctr[kCtrWords];

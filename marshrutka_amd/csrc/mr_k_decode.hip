@@ -211,17 +211,18 @@ __global__ void wire_kernel(const OutResult *__restrict__ res, const OutCmd *__r
     }
 }
 
+// Rows in record order for mr_plan_wire_records (mc < kWireOvf: the header's code carries no
+// longer in-slot count, so a row has at most 127 words).  Always staged: 256 threads while
+// their rows fit 64 KB of LDS (mc <= 31), else 64 (at most 32 512 B).
 hipError_t launch_wire(const OutResult *res, const OutCmd *slots, const OutCmd *ovf, const uint32_t *nov, uint32_t ovf_cap,
-                       uint32_t nrec, uint32_t nq, uint32_t mc, const uint32_t *q_id, uint32_t *rows, uint32_t *wpool,
-                       uint32_t wpool_cap, hipStream_t stream) {
-    const uint32_t nrow = q_id ? nrec : nq;
-    if (!nrow) return hipSuccess;
-    // (staged rows: 256 threads while their rows fit 64 KB of LDS, else 64, else unstaged)
+                       uint32_t nrec, uint32_t nq, uint32_t mc, uint32_t *rows, uint32_t *wpool, uint32_t wpool_cap,
+                       hipStream_t stream) {
+    if (!nq) return hipSuccess;
+    if (mc >= kWireOvf) return hipErrorInvalidValue;
     const uint32_t rw = 1u + 2u * mc, bd = rw <= 64u ? 256u : 64u;
-    const bool stage = !q_id && size_t(bd) * rw * 4 <= 65536;
-    const uint32_t blocks = std::max(1u, std::min(8192u, (nrow + bd - 1) / bd));
-    hipLaunchKernelGGL(wire_kernel, dim3(blocks), dim3(bd), stage ? size_t(bd) * rw * 4 : 0, stream, res, slots, ovf, nov,
-                       ovf_cap, nrec, nq, mc, q_id, nullptr, rows, wpool, wpool_cap, stage);
+    const uint32_t blocks = std::max(1u, std::min(8192u, (nq + bd - 1) / bd));
+    hipLaunchKernelGGL(wire_kernel, dim3(blocks), dim3(bd), size_t(bd) * rw * 4, stream, res, slots, ovf, nov, ovf_cap, nrec,
+                       nq, mc, nullptr, nullptr, rows, wpool, wpool_cap, true);
     return hipGetLastError();
 }
 

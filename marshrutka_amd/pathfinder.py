@@ -555,7 +555,9 @@ class Plan:
     def wire_records(self, d_rows: int, d_pool: int = 0, pool_cap: int = 0, stream=None) -> None:
         """Enqueues the wire encoding of the last pass (mr_plan_wire_records) into caller
         device memory: n rows of wire_row_words(max_cmds) words at d_rows and the pool of
-        long labels (pool_cap commands, 8 B each) at d_pool — what a gather then moves."""
+        long labels (pool_cap commands, 8 B each) at d_pool — what a gather then moves.
+        Wire records exist for plans of max_cmds <= 63 only (a row's first word counts its
+        commands in a 7-bit code): a plan with more slots raises MR_ERR_INVALID_ARG."""
         st = lib().mr_plan_wire_records(self.handle, C.c_void_p(d_rows), C.c_void_p(d_pool) if d_pool else None,
                                         pool_cap, C.c_void_p(stream) if stream else None)
         if st != MR_OK:

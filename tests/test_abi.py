@@ -198,76 +198,54 @@ def test_decode_wire_matches_decode_records(eng, ff, rg):
     """Random command chains of every kind: the wire decoder's recomputed metrics
     (Fleetfoot ceil per StandardMove run, caravan time and coefficient, scroll prices)
     and commands equal mr_decode_records over the same labels with the metrics given."""
-    import random as _r
-    from fractions import Fraction
-
-    import numpy as np
+    from crafted_records import craft
     m = SyntheticMap(15, campfires_per_homeland=3, seed=ff + 11)
     g = eng.MapGrid(m.cells())
     V = len(m.all_indices())
     p = Params(fleetfoot=ff, route_guru=rg, scroll_of_escape_cost=7, scroll_of_escape_hq_cost=11,
                scroll_of_escape_forum_cost=13)
-    ffr = {0: Fraction(1), 1: Fraction(50, 53), 2: Fraction(100, 109), 3: Fraction(25, 28)}.get(ff, Fraction(1))
-    rgt = {0: 240, 1: 190, 2: 168, 3: 146, 4: 124, 5: 102}[rg]  # ceil(240 * RouteGuru ratio)
-    rng = _r.Random(ff * 31 + rg)
     n, mc = 300, 3
-    res = np.zeros((n, 4), dtype=np.uint32)
-    slots = np.zeros((n, mc, 4), dtype=np.uint32)
-    rows = np.zeros((n, 1 + 2 * mc), dtype=np.uint32)
-    ovf, wpool = [], []
-    for k in range(n):
-        if rng.random() < 0.05:
-            res[k, 3] = 17 << 16
-            rows[k, 0] = (65 + 32 + 1) << 25
-            continue
-        nc = rng.randint(0, 6)
-        at = rng.randrange(V)
-        first = at
-        legs = money = t = 0
-        seq = []
-        for _ in range(nc):
-            kind = rng.randint(1, 6)
-            if kind == 1:
-                pay = rng.randint(1, 20)
-                t += 10 * pay
-            elif kind == 2:
-                pay = rng.randint(1, 400)
-                legs += pay
-                t += -((-ffr * 180 * pay).numerator // (ffr * 180 * pay).denominator)
-            elif kind == 3:
-                d, five = rng.randint(1, 600), rng.randint(0, 1)
-                pay = d << 1 | five
-                t += rgt * d
-                money += d * (5 if five else 2)
-            else:
-                pay = 0
-                money += {4: 7, 5: 11, 6: 13}[kind]
-            to = rng.randrange(V)
-            seq.append([(kind << 29) | pay, at, to, 0])
-            at = to
-        res[k] = [legs, money, t, (16 << 16) | nc]
-        if nc <= mc:
-            slots[k, :nc] = seq if nc else 0
-            rows[k, 0] = (first if nc else 0) | nc << 25
-            for j, s_ in enumerate(seq):
-                rows[k, 1 + 2 * j:3 + 2 * j] = [s_[0], s_[2]]
-        else:
-            res[k, 3] = (80 << 16) | nc
-            slots[k, 0] = [0xFFFFFFFF, len(ovf), nc, 0]
-            rows[k, 0] = first | 64 << 25
-            rows[k, 1:3] = [len(ovf), nc]
-            ovf += seq
-            wpool += [[s_[0], s_[2]] for s_ in seq]
-    ovf = np.array(ovf, dtype=np.uint32).reshape(-1, 4)
-    wpool = np.array(wpool, dtype=np.uint32).reshape(-1, 2)
-    a_out, a_pool = eng.decode_records_raw(g, p, res, slots, n, mc, ovf)
-    b_out, b_pool = eng.decode_wire_raw(g, p, rows, n, mc, wpool)
+    c = craft(n, mc, range(0, 7), V, p, seed=ff * 31 + rg)
+    a_out, a_pool = eng.decode_records_raw(g, p, c.res, c.slots, n, mc, c.ovf)
+    b_out, b_pool = eng.decode_wire_raw(g, p, c.rows, n, mc, c.wpool)
     for k in range(n):
         fa = [getattr(a_out[k], f) for f, _ in a_out[k]._fields_]
         fb = [getattr(b_out[k], f) for f, _ in b_out[k]._fields_]
         assert fa == fb, k
     ncmd = sum(a_out[k].n_commands for k in range(n))
     assert bytes(memoryview(a_pool)[:ncmd]) == bytes(memoryview(b_pool)[:ncmd])
+
+
+WIDE_PARAMS = [Params(),
+               Params(fleetfoot=2, sort_by=(abi.SORT_TIME, abi.SORT_MONEY), route_guru=3, scroll_of_escape_cost=7,
+                      scroll_of_escape_hq_cost=11, scroll_of_escape_forum_cost=13)]
+
+
+@pytest.mark.parametrize("params", WIDE_PARAMS, ids=["default", "ff2-time-rg3"])
+@pytest.mark.parametrize("mc", [31, 32, 63])
+def test_host_decoders_at_wide_max_cmds(eng, mc, params):
+    """mr_decode_records and mr_decode_wire at the widths where the wire encoder changes
+    shape (31: the last 256-thread staged row, 32: the first 64-thread one, 63: the largest
+    in-slot count the wire header's 7-bit code carries) over crafted records: labels of 0,
+    1, mc - 1, mc and mc + 1 commands among random lengths up to mc + 8 (the longer ones
+    in the pools), and NOT_FOUND records.  Both equal the crafted labels: every mr_result
+    field, and the command pool byte for byte."""
+    from crafted_records import assert_same_bytes, cells_by_rank, craft, decoded_labels, edge_lengths
+    m = SyntheticMap(15, campfires_per_homeland=3, seed=11)
+    g = eng.MapGrid(m.cells())
+    cells = cells_by_rank(m)
+    n = 300
+    c = craft(n, mc, range(0, mc + 9), len(cells), params, seed=1000 + mc)
+    want = c.labels()
+    lens = {len(w[3]) for w in want if w is not None}
+    assert set(edge_lengths(mc, True)) <= lens and sum(w is None for w in want) >= 3
+    assert len(c.ovf) > mc and (c.res[:, 3] >> 16 == 80).sum() >= 5
+    want_res, want_pool, want_st = c.pack(cells)
+    assert want_st == abi.MR_OK
+    for what, (out, pool) in (("mr_decode_records", eng.decode_records_raw(g, params, c.res, c.slots, n, mc, c.ovf)),
+                              ("mr_decode_wire", eng.decode_wire_raw(g, params, c.rows, n, mc, c.wpool))):
+        assert decoded_labels(out, pool, n, cells) == want, what
+        assert_same_bytes(out, pool, want_res, want_pool, what)
 
 
 def test_labels_digest_follows_query_order(eng):

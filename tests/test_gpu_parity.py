@@ -750,8 +750,8 @@ def test_device_fetch_matches_host_decode(eng, monkeypatch, max_cmds):
                 monkeypatch.setenv("MR_HOST_DECODE", "1")
             else:
                 monkeypatch.delenv("MR_HOST_DECODE", raising=False)
-            # "wire" (the default): rows re-encoded on the device, decoded on the host
-            # pool; "device" / "pinned": the device decoder (MR_FETCH_WIRE=0)
+            # "wire" (opt-in, MR_FETCH_WIRE=1): rows re-encoded on the device, decoded on the
+            # host pool; "device" / "pinned": the device decoder, the default (MR_FETCH_WIRE=0)
             monkeypatch.setenv("MR_FETCH_WIRE", "1" if mode == "wire" else "0")
             plan = eng.Plan(g, params, qs, max_cmds=max_cmds)
             plan.run()
