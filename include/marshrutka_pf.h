@@ -46,7 +46,13 @@ typedef enum mr_status {
                                   reference panics here (src/grid.rs:288-290)    */
     MR_ERR_CAPACITY = -4,      /* caller's command buffer too small; n written   */
     MR_ERR_DEVICE = -5,        /* HIP runtime error                              */
-    MR_ERR_LIMIT = -6,         /* grid or label exceeds an engine limit           */
+    MR_ERR_LIMIT = -6,         /* grid or label exceeds an engine limit.  Metrics
+                                  are 32 bits: a plan returns this when any label
+                                  or candidate (a label plus one edge) its search
+                                  forms exceeds them, even one that would not have
+                                  won; it never returns a wrapped label.  Scroll
+                                  prices are the one input that can reach it
+                                  (legs and time are bounded by the grid)        */
     MR_ERR_NO_DEVICE = -7      /* no gfx950 device visible: the engine has no CPU
                                   fallback and fails loudly                       */
 } mr_status;

@@ -141,8 +141,12 @@ def agg_of_edge(kind, car, costs, ff):
 
 
 class Finder:
-    def __init__(self, grid: Grid, params: dict):
+    def __init__(self, grid: Grid, params: dict, wrap: bool = True):
+        """wrap: u32 legs and money sums wrap like the reference's release build.  With
+        wrap=False they are exact integers (weights stay non-negative, so the search ends
+        whatever the prices are): the reference for inputs whose sums pass 2^32."""
         self.g = grid
+        self.mask = U32 if wrap else -1
         p = params
         self.costs = {SOE: p["scroll_of_escape_cost"], SHQ: p["scroll_of_escape_hq_cost"],
                       SFM: p["scroll_of_escape_forum_cost"]}
@@ -169,7 +173,7 @@ class Finder:
             coef = 5
         t = skill(RG_TABLE, self.rg, 240)
         t = 240 if t is None else t
-        return (t * d, (coef * d) & U32)
+        return (t * d, (coef * d) & self.mask)
 
     def edges(self, v):
         H = self.g.size // 2
@@ -228,8 +232,8 @@ class Finder:
             agg = agg_of_edge(kind, car, self.costs, self.ff)
             frm = v
         cmds.append((agg, frm, w))
-        legs = sum(agg_legs(c[0]) for c in cmds) & U32
-        money = sum(agg_money(c[0]) for c in cmds) & U32
+        legs = sum(agg_legs(c[0]) for c in cmds) & self.mask
+        money = sum(agg_money(c[0]) for c in cmds) & self.mask
         time = sum(agg_time(c[0]) for c in cmds)
         return (legs, money, time, tuple(cmds))
 

@@ -13,7 +13,9 @@ the records a pass could have written for labels of any length up to max_cmds an
 and the labels they stand for, which are the reference: metrics summed in Python integers,
 the Fleetfoot time of a StandardMove run as a Fraction's ceiling, nothing taken from the
 library.  A chain keeps from[j] == to[j-1], kinds 1..6, ranks < V, and payloads small
-enough that 4096 commands sum to less than 2^30 in every metric.
+enough that 4096 commands sum to less than 2^30 in legs and time.  Money is the one metric
+a caller's prices can push to the top of 32 bits: with max_scrolls a record holds at most
+that many scrolls, so prices above 2^30 give label money past 2^31 and still below 2^32.
 """
 from fractions import Fraction
 
@@ -26,6 +28,12 @@ from marshrutka_amd.abi import MR_ERR_INVALID_INDEX, MR_NOT_FOUND, MR_OK
 FLEETFOOT = {0: Fraction(1), 1: Fraction(50, 53), 2: Fraction(100, 109), 3: Fraction(25, 28)}
 CARAVAN_UNIT = {0: 240, 1: 190, 2: 168, 3: 146, 4: 124, 5: 102}
 MAX_CENTRAL, MAX_STANDARD, MAX_CARAVAN = 20, 400, 600  # payload bounds
+
+# prices that put a label's money past 2^31 with three scrolls (4.2e9, below 2^32 with 4096
+# caravans of at most 3000 on top): craft(..., max_scrolls=LARGE_MONEY_SCROLLS)
+LARGE_MONEY_PRICES = dict(scroll_of_escape_cost=1_400_000_000, scroll_of_escape_hq_cost=1_399_999_999,
+                          scroll_of_escape_forum_cost=1_399_999_998)
+LARGE_MONEY_SCROLLS = 3
 
 ST_OK, ST_NOT_FOUND, ST_OVERFLOW = 16 << 16, 17 << 16, 80 << 16  # the records' status half-word
 OVF_TAG = 0xFFFFFFFF
@@ -136,14 +144,16 @@ class Crafted:
         return res, pool, (MR_OK if has.all() else MR_ERR_INVALID_INDEX)
 
 
-def craft(n, max_cmds, lengths, V, params, seed, overflow=True, not_found=None):
+def craft(n, max_cmds, lengths, V, params, seed, overflow=True, not_found=None, max_scrolls=None):
     """n records for a plan of max_cmds command slots over a grid of V cells.
 
     lengths: the command counts to draw from, uniformly.  Whatever it holds, the counts of
     edge_lengths() come first (as many as n has room for), at random records.  overflow:
     counts above max_cmds are kept and go to the overflow pool / wire pool; without it
     they are cut to max_cmds (a test that cannot write a plan's pool).  not_found: how many
-    records are NOT_FOUND (default: n / 20, at least 3 where n has room)."""
+    records are NOT_FOUND (default: n / 20, at least 3 where n has room).  max_scrolls: at
+    most that many commands of kinds 4..6 (the scrolls, whose money is the caller's price)
+    in a record; the scrolls past them are redrawn from kinds 1..3."""
     rng = np.random.default_rng(seed)
     edges = edge_lengths(max_cmds, overflow)[:n]
     if not_found is None:
@@ -162,6 +172,12 @@ def craft(n, max_cmds, lengths, V, params, seed, overflow=True, not_found=None):
 
     # the chains: a kind, its payload, the cell each command ends in
     kind = rng.integers(1, 7, T)
+    if max_scrolls is not None:  # (a generator of its own: the other draws stay what they were)
+        is_scroll = kind >= 4
+        seen = np.cumsum(is_scroll)
+        nth = seen - np.repeat((seen - is_scroll)[start[ncmd > 0]], ncmd[ncmd > 0])  # within its record
+        extra = is_scroll & (nth > max_scrolls)
+        kind[extra] = np.random.default_rng([seed, 1]).integers(1, 4, int(extra.sum()))
     d = rng.integers(1, MAX_CARAVAN + 1, T)
     five = rng.integers(0, 2, T)
     pay = np.select([kind == 1, kind == 2, kind == 3],
@@ -197,7 +213,7 @@ def craft(n, max_cmds, lengths, V, params, seed, overflow=True, not_found=None):
         c.legs.append(sum(c_legs[a:b].tolist()))
         c.money.append(sum(c_money[a:b].tolist()))
         c.time_s.append(sum(l_time[a:b].tolist()))
-    assert max(c.legs + c.money + c.time_s + [0]) < 1 << 30
+    assert max(c.legs + c.time_s + [0]) < 1 << 30 and max(c.money + [0]) < 1 << 32
 
     # the layouts.  A compact command: {kind << 29 | payload, from, to, 0}
     kp = (kind << 29 | pay).astype(np.uint32)

@@ -8,6 +8,7 @@ import re
 import pytest
 
 from marshrutka_amd import abi
+from crafted_records import LARGE_MONEY_PRICES, LARGE_MONEY_SCROLLS
 from marshrutka_amd.abi import BLUE, CellIndex, Params
 from marshrutka_amd.mapgen import SyntheticMap, to_html
 
@@ -218,12 +219,16 @@ def test_decode_wire_matches_decode_records(eng, ff, rg):
 
 WIDE_PARAMS = [Params(),
                Params(fleetfoot=2, sort_by=(abi.SORT_TIME, abi.SORT_MONEY), route_guru=3, scroll_of_escape_cost=7,
-                      scroll_of_escape_hq_cost=11, scroll_of_escape_forum_cost=13)]
+                      scroll_of_escape_hq_cost=11, scroll_of_escape_forum_cost=13),
+               # three scrolls a record at 1.4e9 each: label money up to 4.2e9, bit 31 set
+               Params(fleetfoot=1, sort_by=(abi.SORT_MONEY, abi.SORT_LEGS), route_guru=2, **LARGE_MONEY_PRICES)]
+WIDE_MAX_SCROLLS = [None, None, LARGE_MONEY_SCROLLS]
 
 
-@pytest.mark.parametrize("params", WIDE_PARAMS, ids=["default", "ff2-time-rg3"])
+@pytest.mark.parametrize("params,max_scrolls", list(zip(WIDE_PARAMS, WIDE_MAX_SCROLLS)),
+                         ids=["default", "ff2-time-rg3", "money-4.2e9"])
 @pytest.mark.parametrize("mc", [31, 32, 63])
-def test_host_decoders_at_wide_max_cmds(eng, mc, params):
+def test_host_decoders_at_wide_max_cmds(eng, mc, params, max_scrolls):
     """mr_decode_records and mr_decode_wire at the widths where the wire encoder changes
     shape (31: the last 256-thread staged row, 32: the first 64-thread one, 63: the largest
     in-slot count the wire header's 7-bit code carries) over crafted records: labels of 0,
@@ -235,8 +240,10 @@ def test_host_decoders_at_wide_max_cmds(eng, mc, params):
     g = eng.MapGrid(m.cells())
     cells = cells_by_rank(m)
     n = 300
-    c = craft(n, mc, range(0, mc + 9), len(cells), params, seed=1000 + mc)
+    c = craft(n, mc, range(0, mc + 9), len(cells), params, seed=1000 + mc, max_scrolls=max_scrolls)
     want = c.labels()
+    if max_scrolls is not None:  # the set is there for money words with bit 31 set
+        assert sum(w is not None and w[1] >= 1 << 31 for w in want) >= n // 4
     lens = {len(w[3]) for w in want if w is not None}
     assert set(edge_lengths(mc, True)) <= lens and sum(w is None for w in want) >= 3
     assert len(c.ovf) > mc and (c.res[:, 3] >> 16 == 80).sum() >= 5

@@ -13,11 +13,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from crafted_records import (WIRE_RANK_BITS, WIRE_STATUS, assert_same_bytes, cells_by_rank, craft, decoded_labels,
-                             edge_lengths)
+from crafted_records import (LARGE_MONEY_PRICES, LARGE_MONEY_SCROLLS, WIRE_RANK_BITS, WIRE_STATUS, assert_same_bytes,
+                             cells_by_rank, craft, decoded_labels, edge_lengths)
 from golden_util import as_expected
 from marshrutka_amd.abi import (BLUE, MR_ERR_CAPACITY, MR_ERR_INVALID_ARG, MR_ERR_INVALID_INDEX, MR_NOT_FOUND, MR_OK,
-                                SORT_MONEY, SORT_TIME, CellIndex, Params, mr_command, mr_result)
+                                SORT_LEGS, SORT_MONEY, SORT_TIME, CellIndex, Params, mr_command, mr_result)
 from marshrutka_amd.mapgen import SyntheticMap, random_queries
 
 pytestmark = pytest.mark.gpu
@@ -26,10 +26,14 @@ H2D, D2H = 1, 2  # hipMemcpyKind
 WIRE_MAX_CMDS = 63  # the wire header's 7-bit code: in-slot counts 0 .. 63
 PARAMS = [Params(),
           Params(fleetfoot=2, sort_by=(SORT_TIME, SORT_MONEY), route_guru=3, scroll_of_escape_cost=7,
-                 scroll_of_escape_hq_cost=11, scroll_of_escape_forum_cost=13)]
+                 scroll_of_escape_hq_cost=11, scroll_of_escape_forum_cost=13),
+          # three scrolls a record at 1.4e9 each: label money up to 4.2e9, bit 31 set
+          Params(fleetfoot=1, sort_by=(SORT_MONEY, SORT_LEGS), route_guru=2, **LARGE_MONEY_PRICES)]
 # n: 65 is one past a 64-thread workgroup, 257 one past a 256-thread one, 600 a multiple
 # of neither; 4096 slots with a few full-length labels only
 CASES = [(mc, n) for mc in (31, 32, 63, 64, 128) for n in (1, 65, 257, 600)] + [(4096, 65)]
+# the large-money set once per shape of the wire encoder and of the device decoder
+MONEY_CASES = [(31, 257), (32, 600), (63, 65), (64, 257), (128, 65), (4096, 65)]
 OUTSIDE = (CellIndex.center(), CellIndex.homeland(BLUE, 99, 99))  # names no cell of the grid
 
 
@@ -84,9 +88,12 @@ def _clear_env(monkeypatch):
         monkeypatch.delenv(v, raising=False)
 
 
-@pytest.mark.parametrize("mc,n,params", [(mc, n, PARAMS[i % 2]) for i, (mc, n) in enumerate(CASES)],
-                         ids=[f"mc{mc}-n{n}-{'ff2' if i % 2 else 'default'}" for i, (mc, n) in enumerate(CASES)])
-def test_fetch_routes_decode_crafted_records(eng, hip, monkeypatch, mc, n, params):
+@pytest.mark.parametrize("mc,n,params,max_scrolls",
+                         [(mc, n, PARAMS[i % 2], None) for i, (mc, n) in enumerate(CASES)]
+                         + [(mc, n, PARAMS[2], LARGE_MONEY_SCROLLS) for mc, n in MONEY_CASES],
+                         ids=[f"mc{mc}-n{n}-{'ff2' if i % 2 else 'default'}" for i, (mc, n) in enumerate(CASES)]
+                         + [f"mc{mc}-n{n}-money4.2e9" for mc, n in MONEY_CASES])
+def test_fetch_routes_decode_crafted_records(eng, hip, monkeypatch, mc, n, params, max_scrolls):
     """n crafted records (and 3 queries outside the grid: rows past the records) at
     max_cmds mc, through every route.  launch_wire runs 256 threads a workgroup up to
     mc 31 (64 512 B of LDS at 31, its largest request) and 64 up to 63; above that the
@@ -108,8 +115,10 @@ def test_fetch_routes_decode_crafted_records(eng, hip, monkeypatch, mc, n, param
     assert all(q == 0xFFFFFFFF for q in q_of[nrec:])
 
     lengths = list(range(100)) + [mc] * 6 if mc == 4096 else range(mc + 1)
-    c = craft(nrec, mc, lengths, len(cells), params, seed=7 * mc + n, overflow=False)
+    c = craft(nrec, mc, lengths, len(cells), params, seed=7 * mc + n, overflow=False, max_scrolls=max_scrolls)
     labels = c.labels()
+    if max_scrolls is not None:  # the set is there for money words with bit 31 set
+        assert sum(w is not None and w[1] >= 1 << 31 for w in labels) >= nrec // 4
     lens = [len(w[3]) for w in labels if w is not None]
     assert set(edge_lengths(mc, False)[:nrec]) <= set(lens) and max(lens) <= mc
     if mc == 4096:
