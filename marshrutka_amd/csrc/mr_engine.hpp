@@ -228,7 +228,16 @@ struct KArgs {
     // (mr_hub_lane.hpp), built once per (grid, params) by hub_lane_build_kernel and read by
     // hub_lane_memo_kernel; null: the plan runs hub_lane_kernel
     uint32_t *lane_memo;
+    // the memo's winner table (DESIGN.md section 3a'''): per cell a word with 5 bits per
+    // region row (kLaneWinBits; region r at bit 5 r), the boundary entry whose walk is the
+    // best one into that cell from the region's row, kLaneWinNone where the read-off has to
+    // run the candidates itself; and per cell the region row it lies in at distance 0
+    // (kLaneRegNone: none).  Built by hub_lane_win_kernel; null: the memo kernel runs the
+    // candidates for every destination
+    uint32_t *lane_win;
+    uint8_t *lane_reg0;
 };
+constexpr uint32_t kLaneWinBits = 5u, kLaneWinNone = 31u, kLaneRegNone = 255u;
 // cert_redo[slot]: kRedoFill — promoted specials: the closed form again, both checks and the
 // repair; kRedoSweep — specials the last check demoted: the repair from the current words
 // and the last check only

@@ -51,8 +51,10 @@ hipError_t launch_hub_lane(const KArgs *d_args, const uint32_t perm[3], uint32_t
 uint32_t lane_memo_words(uint32_t NS, uint32_t nreg);
 hipError_t launch_lane_memo_build(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg,
                                   hipStream_t stream);
+hipError_t launch_lane_win_build(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t V,
+                                 hipStream_t stream);
 hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
-                                hipStream_t stream);
+                                bool win, hipStream_t stream);
 uint32_t hub_group_slots(uint32_t NS, uint32_t G);
 uint32_t lane_blob_build(const SpecialStatic *sp, uint32_t NS, uint32_t nreg, uint32_t TM, uint32_t rgt,
                          uint32_t ff_num, uint32_t ff_den, const uint32_t *near_sp, std::vector<uint32_t> &blob);
@@ -230,13 +232,25 @@ struct mr_grid {
     // lane memo (lane_memo_rows): the specials' tables per SoE region and per special cell,
     // built on the device once per (device, homeland, HQ cell, params) and shared by the
     // grid's plans; `gate`: the rows stand for every source (else `why` says what failed)
+    // Under the gate a memo also holds the winner table (lane_win_table): per cell a word
+    // with each region row's best boundary, and per cell the region row it lies in.  The
+    // cache is bounded by its keys and by the bytes its entries hold (kLaneMemoCacheBytes).
     struct LaneMemo {
         DevBuf<uint32_t> d_rows;
         bool gate = false;
         std::string why;
+        std::vector<uint32_t> srcs;  // the rows' sources: a plain cell per region, then the specials' cells
+        DevBuf<uint32_t> d_win;
+        DevBuf<uint8_t> d_reg0;
+        size_t bytes() const { return d_rows.size() * 4 + d_win.size() * 4 + d_reg0.size(); }
     };
     mutable std::mutex memo_mu;
     mutable std::map<std::string, std::shared_ptr<LaneMemo>> lane_memo;
+    size_t lane_memo_bytes() const {  // (the caller holds memo_mu)
+        size_t b = 0;
+        for (const auto &kv : lane_memo) b += kv.second->bytes();
+        return b;
+    }
     // device copies of the region tables, built on first use and shared by the grid's
     // plans (the grid outlives its plans): one per (device, homeland), so a plan never
     // reads a table that lives on another device
@@ -1869,6 +1883,7 @@ static std::shared_ptr<mr_grid::LaneMemo> lane_memo_rows(const mr_grid *g, int d
         (void)hipGetLastError();
         return nullptr;
     }
+    m->srcs = srcs;
     // the gate: every row certified, every entry of a region's row strictly below the
     // one-leg walk on the metrics in the plan's order
     const uint32_t leg[3] = {1u, 0u, 180u};
@@ -1890,6 +1905,63 @@ static std::shared_ptr<mr_grid::LaneMemo> lane_memo_rows(const mr_grid *g, int d
         }
     }
     return keep();
+}
+
+// The winner table's bytes on a grid of V cells (a word and a byte per cell), and what one
+// table may take: plans on a grid past the budget keep the read-off that runs the
+// candidates (4097^2: 84 MB).  MR_LANE_WIN_BUDGET overrides the budget (bytes; tests force 0).
+static size_t lane_win_bytes(uint32_t V) { return size_t(V) * 5; }
+constexpr size_t kLaneWinBudget = size_t(96) << 20;
+// what the memos cached on one grid may hold together (a plan holds its own memo, so
+// clearing the cache frees a memo when its last plan goes)
+constexpr size_t kLaneMemoCacheBytes = size_t(256) << 20;
+static size_t lane_win_budget() {
+    if (const char *e = std::getenv("MR_LANE_WIN_BUDGET")) return size_t(std::strtoull(e, nullptr, 10));
+    return kLaneWinBudget;
+}
+
+// The winner table of a gated memo (DESIGN.md section 3a'''), built on first use: the best
+// boundary walk into a plain cell depends on a non-special source only through its region
+// row, so hub_lane_win_kernel finds it once per (row, cell) and hub_lane_memo_kernel reads
+// it.  false: a device error.  `why`: set where the table is not to be used.
+static bool lane_win_table(const mr_grid *g, mr_grid::LaneMemo &m, const HostPlan &hp, const KArgs &ka, hipStream_t stream,
+                           std::string &why) {
+    std::lock_guard<std::mutex> lk(g->memo_mu);
+    if (lane_win_bytes(g->V) > lane_win_budget()) {
+        why = "the table is over its byte budget";
+        return true;
+    }
+    if (m.d_win) return true;
+    // (the plan holds m: clearing the cache frees only memos no plan uses)
+    if (g->lane_memo_bytes() + lane_win_bytes(g->V) > kLaneMemoCacheBytes) g->lane_memo.clear();
+    const uint32_t nrows = uint32_t(m.srcs.size());
+    DevBuf<uint32_t> d_src, d_win;
+    DevBuf<uint8_t> d_reg0;
+    DevBuf<KArgs> d_kb;
+    KArgs kb = ka;
+    bool ok = nrows == hp.nreg + hp.p.NS && d_win.alloc(g->V, DevMem::direct) == hipSuccess &&
+              d_reg0.alloc(g->V, DevMem::direct) == hipSuccess && d_src.alloc(nrows, DevMem::direct) == hipSuccess &&
+              d_kb.alloc(1, DevMem::direct) == hipSuccess;
+    if (ok) {
+        kb.src_v = d_src.get();
+        kb.n_lane = nrows;
+        kb.lane_memo = m.d_rows.get();
+        kb.lane_win = d_win.get();
+        kb.lane_reg0 = d_reg0.get();
+        kb.relist = nullptr;
+        kb.dbg = nullptr;
+        ok = hipMemcpy(d_src.get(), m.srcs.data(), size_t(nrows) * 4, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(d_kb.get(), &kb, sizeof(KArgs), hipMemcpyHostToDevice) == hipSuccess &&
+             launch_lane_win_build(d_kb.get(), hp.p.perm, hp.p.NS, hp.nreg, g->V, stream) == hipSuccess &&
+             hipStreamSynchronize(stream) == hipSuccess;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        return false;
+    }
+    m.d_win = std::move(d_win);
+    m.d_reg0 = std::move(d_reg0);
+    return true;
 }
 
 // sources that would run on the lane kernel (at most kLaneMaxQ queries)
@@ -2320,6 +2392,8 @@ static void plan_base_args(mr_plan *pl, uint32_t n) {
     ka.dbg = nullptr;
     ka.near = nullptr;
     ka.lane_memo = nullptr;
+    ka.lane_win = nullptr;
+    ka.lane_reg0 = nullptr;
     ka.nreg = 0;
     ka.fb_mode = 0;
     ka.fb_all = env_fallback_all() ? 1u : 0u;  // tests cover the fallback path
@@ -2513,6 +2587,21 @@ static int plan_lane_memo(mr_plan *pl) {
     }
     if (env_is("MR_LANE_MEMO", "require") && !pl->ka.lane_memo)
         return fail(MR_ERR_INVALID_ARG, "MR_LANE_MEMO=require: " + why);
+    // The winner table: the memo kernel reads each destination's best boundary instead of
+    // running the candidates.  MR_LANE_WIN=0: never; =require: plan creation fails where
+    // the table is not used.
+    std::string wwhy = pl->ka.lane_memo ? "switched off" : "no lane memo (" + why + ")";
+    if (pl->ka.lane_memo && !env_is("MR_LANE_WIN", "0")) {
+        wwhy.clear();
+        if (!lane_win_table(pl->grid, *pl->hub.memo, hp, slot_args(pl, 0), pl->stream.get(), wwhy))
+            return fail(MR_ERR_DEVICE, "lane winner table");
+        if (wwhy.empty()) {
+            pl->ka.lane_win = pl->hub.memo->d_win.get();
+            pl->ka.lane_reg0 = pl->hub.memo->d_reg0.get();
+        }
+    }
+    if (env_is("MR_LANE_WIN", "require") && !pl->ka.lane_win)
+        return fail(MR_ERR_INVALID_ARG, "MR_LANE_WIN=require: " + wwhy);
     return MR_OK;
 }
 
@@ -2740,7 +2829,7 @@ static hipError_t run_hub(mr_plan *pl, hipStream_t s) {
         const KArgs *la = (pl->fb_none && !big ? h.args_lane_last : h.args_lane).get();
         // (a plan whose memo gate held: the destinations only, from the grid's rows)
         if (h.lane_g) e = launch_hub_group(la, perm, NS, nreg, h.n_lane, h.lane_g, pl->hp.nonlin, s);
-        else if (pl->ka.lane_memo) e = launch_hub_lane_memo(la, perm, NS, nreg, h.n_lane, s);
+        else if (pl->ka.lane_memo) e = launch_hub_lane_memo(la, perm, NS, nreg, h.n_lane, pl->ka.lane_win != nullptr, s);
         else e = launch_hub_lane(la, perm, NS, nreg, h.n_lane, pl->hp.nonlin, s);
     }
     if (e == hipSuccess && big) e = launch_hub_plan(pl, pl->fb_none ? h.args_hub_last.get() : args, s);

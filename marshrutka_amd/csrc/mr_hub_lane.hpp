@@ -289,7 +289,9 @@ __device__ __forceinline__ uint32_t ltm3(const LLab &x, const LLab &y) {
 //               table every non-special source of that region shares when the gate
 //               holds (lane_memo_rows, mr_host.cpp)
 //   kLaneMemo   destinations only: the table is the source's memo row (LDS)
-constexpr uint32_t kLaneSolve = 0, kLaneBuild = 1, kLaneMemo = 2;
+//   kLaneWin    kLaneMemo with the winner table: a plain source's destinations take their
+//               best boundary from the table instead of running the candidates
+constexpr uint32_t kLaneSolve = 0, kLaneBuild = 1, kLaneMemo = 2, kLaneWin = 3;
 // A memo row: entry t's label at words 4 t .. 4 t + 3 (c1, c2, c3, meta; entry 0 is the
 // start label), then {done, bndm, blk, valid}.  Rows 0 .. nreg - 1 are the regions',
 // row nreg + t - 1 is special t's own (an ordinary solve from its cell).
@@ -301,6 +303,7 @@ struct LaneHub {
 #ifdef MR_STAMPS
     unsigned long long lst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lst_last = 0;
 #endif
+    static constexpr bool kRow = MODE == kLaneMemo || MODE == kLaneWin;  // the table is a memo row
     static constexpr uint32_t C1 = PERM / 9, C2 = (PERM / 3) % 3, C3 = PERM % 3;
     const KArgs *__restrict__ a;
     DevParams P;
@@ -322,7 +325,10 @@ struct LaneHub {
     // tentative / settled labels of entries 1..TM-1 (entry 0, the source, is the start label)
     LLab L[TM];
     uint32_t tent = 0, done = 0, wt = 0, bndm = 0, blk = 0;
-    const uint4 *R = nullptr;  // kLaneMemo: this lane's memo row (LDS), read in place of L
+    const uint4 *R = nullptr;  // kLaneMemo, kLaneWin: this lane's memo row (LDS), read in place of L
+    // kLaneWin: the source's region in a winner word (a shift), and kLaneWinNone where the
+    // source reads no winners (a special), else 0
+    uint32_t wsh = 0, wnone = kLaneWinNone;
     bool aonly = false;        // kLaneBuild: a region's row (position-independent own edges only)
 
     // ---- metrics in comparator order -------------------------------------------------
@@ -374,7 +380,7 @@ struct LaneHub {
     __device__ __forceinline__ uint2 near_of(uint32_t p, uint32_t r) const { return p == 0 ? srow[r] : nearS[p * nreg + r]; }
     // entry e's label (run-time e; a select per entry: the rare paths only)
     __device__ __forceinline__ LLab get(uint32_t e) const {
-        if constexpr (MODE == kLaneMemo) {
+        if constexpr (kRow) {
             const uint4 q = R[e];
             return LLab{q.x, q.y, q.z, q.w};
         }
@@ -385,7 +391,7 @@ struct LaneHub {
     }
     // entry t's label where t is a constant of an unrolled loop
     __device__ __forceinline__ LLab lab(uint32_t t) const {
-        if constexpr (MODE == kLaneMemo) {
+        if constexpr (kRow) {
             const uint4 q = R[t];
             return LLab{q.x, q.y, q.z, q.w};
         }
@@ -438,7 +444,7 @@ struct LaneHub {
     const uint2 *HT;     // LDS: the specials' cells by hash (lane_hash)
     uint32_t ht_probes;  // the longest probe sequence in HT
     __device__ __forceinline__ void dump_meta() const {
-        if constexpr (MODE == kLaneMemo) return;  // (the row holds the metas)
+        if constexpr (kRow) return;  // (the row holds the metas)
         const uint32_t l = lane_id();
         M[mcolumn] = start().m;
         (void)l;
@@ -446,7 +452,7 @@ struct LaneHub {
         for (uint32_t t = 1; t < TM; ++t) M[t * mstride + mcolumn] = L[t].m;
     }
     __device__ __forceinline__ uint32_t meta_of(uint32_t e) const {
-        if constexpr (MODE == kLaneMemo) return R[e].w;
+        if constexpr (kRow) return R[e].w;
         return M[e * mstride + mcolumn];
     }
     // the meta copy's layout: entry t of this lane's column at t * mstride + mcolumn (the
@@ -1155,6 +1161,75 @@ struct LaneHub {
         MR_LSTAMP(6);  // (6: the certification of settled labels)
         return unc;
     }
+    // The best walk into the plain cell wo: the source's own (walk0) or a boundary's label
+    // plus its walk.  x: the label; bx: the boundary's entry (0: the source's walk,
+    // kNone32: no walk reaches the cell).
+    __device__ __forceinline__ void best_walk(bool walk0, const Own &wo, LLab &x, uint32_t &bx) const {
+        const int wx = wo.x, wy = wo.y;
+        // Every candidate is a boundary's label plus one walk command, so they are compared
+        // on the boundary's own meta word (length - 1; the source's walk: 0) and the walk's
+        // meta is built for the winner.  The clobber and the volatile copy of bndm keep the
+        // per-entry terms inside the callers' query loops (hoisted out of them they would hold
+        // ~170 VGPRs for the whole kernel).
+        asm volatile("" ::: "memory");
+        const uint32_t bq = vvolatile(bndm);
+        x = inf();
+        bx = walk0 ? 0u : kNone32;
+        uint32_t tie = 0;  // the boundaries whose walk ties the best so far exactly (entry bits)
+        {
+            const uint32_t k = walk_dist(sx, sy, wx, wy);
+            ll_sel(vmask(walk0), x, mk(k, 0, rtime(k), 0u));
+        }
+#pragma unroll
+        for (uint32_t t = 2; t < TM; ++t) {
+            const uint32_t k = walk_dist(spl[t].x, spl[t].y, wx, wy);
+            const uint32_t cm = bitm(bq, t);
+            const LLab lt_ = lab(t);
+            const LLab c = opt(cm, add(lt_, k, 0, rtime(k), lt_.m));
+#ifdef MR_LANE_CLASSIC
+            const uint32_t lt = ltm(c, x), gt = ltm(x, c);
+            tie = ~lt & (tie | (cm & ~gt & (1u << t)));
+            ll_sel(lt, x, c);
+            bx = msel(lt, t, bx);
+#else
+            const uint32_t gt = ltm(x, c);
+            const uint32_t lt = ltm_take_idx(c, x, t, bx);
+            tie = ~lt & (tie | (cm & ~gt & (1u << t)));
+#endif
+            MR_LANE_FENCE();
+        }
+        x.m = lm_pack(lm_len(x.m) + 1u, bx == kNone32 ? 0u : bx, 1, kStandard);
+        // Equal metrics and length from several boundaries: the lists decide, among the
+        // boundaries that tied the final best only (a strictly better walk cleared the
+        // set; the source's walk, visited first, is never taken on a tie)
+        if (tie) {
+            for (uint32_t m = tie; m; m &= m - 1u) {
+                const uint32_t b = uint32_t(__builtin_ctz(m));
+                int px, py;
+                pos(b, px, py);
+                const uint32_t k = walk_dist(px, py, wx, wy);
+                const LLab c = b == 0 ? mk(k, 0, rtime(k), lm_pack(1, 0, 1, kStandard)) : walk_to(get(b), b, k);
+                if (cmp4(c, x) == 0 && cmp_list(c.m, kOwn, wo, x.m, kOwn, wo) < 0) {
+                    x = c;
+                    bx = b;
+                }
+            }
+        }
+    }
+    // kLaneWin: boundary e is the best of the row's boundaries into
+    // the plain cell wo (hub_lane_win_kernel ran best_walk for the row without a source's
+    // walk), so the label is its walk or the source's own.  For non-special sources only:
+    // they have a walk of their own.  (The two never tie exactly: the source's walk is one
+    // command, a boundary's at least two, so best_walk's list compare has no case here.)
+    __device__ __forceinline__ void win_walk(uint32_t e, const Own &wo, LLab &x, uint32_t &bx) const {
+        const uint32_t k = walk_dist(spl[e].x, spl[e].y, wo.x, wo.y), ks = walk_dist(sx, sy, wo.x, wo.y);
+        x = walk_to(get(e), e, k);
+        bx = e;
+        const LLab s = mk(ks, 0, rtime(ks), lm_pack(1, 0, 1, kStandard));
+        const uint32_t own = ~ltm(x, s);  // the boundary's walk is not strictly below the source's
+        ll_sel(own, x, s);
+        bx &= ~own;
+    }
     // the source's queries from its settled table; returns the records written
     __device__ __forceinline__ uint32_t read_off(uint32_t s_idx, bool unc) {
         const DevParams &p = P;
@@ -1163,8 +1238,28 @@ struct LaneHub {
         const bool fb_sp = unc || a->fb_all;
         // ---- destinations: the source, a special's own label, or the best walk ------------
         const bool walk0 = src != p.vc;
-        for (uint32_t qi = fb_sp ? qb : qa; qi < qb; ++qi) {
-            const uint32_t w = a->q_dst[qi];
+        const uint32_t q0 = fb_sp ? qb : qa;
+        // kLaneWin: a destination and its winner word are loaded one query ahead, before
+        // the current query's output (a wave's sources have equal query counts)
+        uint32_t wn = 0, wwn = 0;
+        if constexpr (MODE == kLaneWin) {
+            if (q0 < qb) {
+                wn = a->q_dst[q0];
+                wwn = a->lane_win[wn];
+            }
+        }
+        for (uint32_t qi = q0; qi < qb; ++qi) {
+            uint32_t w, e = kLaneWinNone;
+            if constexpr (MODE == kLaneWin) {
+                w = wn;
+                e = ((wwn >> wsh) & kLaneWinNone) | wnone;
+                if (qi + 1 < qb) {
+                    wn = a->q_dst[qi + 1];
+                    wwn = a->lane_win[wn];
+                }
+            } else {
+                w = a->q_dst[qi];
+            }
             const int wx = int(w % p.S) - int(p.H), wy = int(w / p.S) - int(p.H);
             uint32_t tw, wr;
             cell_word(w, wx, wy, tw, wr);
@@ -1177,54 +1272,18 @@ struct LaneHub {
                 continue;
             }
             const Own wo{wx, wy, wr, kNone10, 0u};
-            // Every candidate is a boundary's label plus one walk command, so they are
-            // compared on the boundary's own meta word (length - 1; the source's walk:
-            // 0) and the walk's meta is built for the winner.  The clobber and the
-            // volatile copy of bndm keep the per-entry terms inside the query loop
-            // (hoisted out of it they would hold ~170 VGPRs for the whole kernel).
-            asm volatile("" ::: "memory");
-            const uint32_t bq = vvolatile(bndm);
             LLab x = inf();
-            uint32_t bx = walk0 ? 0u : kNone32;
-            uint32_t tie = 0;  // the boundaries whose walk ties the best so far exactly (entry bits)
-            {
-                const uint32_t k = walk_dist(sx, sy, wx, wy);
-                ll_sel(vmask(walk0), x, mk(k, 0, rtime(k), 0u));
-            }
-#pragma unroll
-            for (uint32_t t = 2; t < TM; ++t) {
-                const uint32_t k = walk_dist(spl[t].x, spl[t].y, wx, wy);
-                const uint32_t cm = bitm(bq, t);
-                const LLab lt_ = lab(t);
-                const LLab c = opt(cm, add(lt_, k, 0, rtime(k), lt_.m));
-#ifdef MR_LANE_CLASSIC
-                const uint32_t lt = ltm(c, x), gt = ltm(x, c);
-                tie = ~lt & (tie | (cm & ~gt & (1u << t)));
-                ll_sel(lt, x, c);
-                bx = msel(lt, t, bx);
-#else
-                const uint32_t gt = ltm(x, c);
-                const uint32_t lt = ltm_take_idx(c, x, t, bx);
-                tie = ~lt & (tie | (cm & ~gt & (1u << t)));
-#endif
-                MR_LANE_FENCE();
-            }
-            x.m = lm_pack(lm_len(x.m) + 1u, bx == kNone32 ? 0u : bx, 1, kStandard);
-            // Equal metrics and length from several boundaries: the lists decide, among the
-            // boundaries that tied the final best only (a strictly better walk cleared the
-            // set; the source's walk, visited first, is never taken on a tie)
-            if (tie) {
-                for (uint32_t m = tie; m; m &= m - 1u) {
-                    const uint32_t b = uint32_t(__builtin_ctz(m));
-                    int px, py;
-                    pos(b, px, py);
-                    const uint32_t k = walk_dist(px, py, wx, wy);
-                    const LLab c = b == 0 ? mk(k, 0, rtime(k), lm_pack(1, 0, 1, kStandard)) : walk_to(get(b), b, k);
-                    if (cmp4(c, x) == 0 && cmp_list(c.m, kOwn, wo, x.m, kOwn, wo) < 0) {
-                        x = c;
-                        bx = b;
-                    }
+            uint32_t bx = kNone32;
+            if constexpr (MODE == kLaneWin) {
+                // the candidates only for the lanes without a winner (a special source, a cell
+                // the table leaves out): ordinary waves skip them
+                const bool slow = e == kLaneWinNone;
+                if (!slow) win_walk(e, wo, x, bx);
+                if (__any(slow)) {
+                    if (slow) best_walk(walk0, wo, x, bx);
                 }
+            } else {
+                best_walk(walk0, wo, x, bx);
             }
             if (bx == kNone32) {  // no boundary can walk here: cannot happen on a connected grid
                 a->out_res[qi] = OutResult{0, 0, 0, uint32_t(16 + 1) << 16};
@@ -1263,12 +1322,15 @@ struct LaneHub {
         for (uint32_t t = 1; t < TM; ++t) o[t] = make_uint4(L[t].c1, L[t].c2, L[t].c3, L[t].m);
         o[TM] = make_uint4(done, bndm, blk, unc ? 0u : 1u);
     }
-    // kLaneMemo: the source's queries from its memo row (rows: the plan's rows in LDS) — a
+    // kLaneMemo, kLaneWin: the source's queries from its memo row (rows: the plan's rows in LDS) — a
     // special's own row, else the row of the region the source lies in (distance 0)
     __device__ __forceinline__ uint32_t memo_solve(uint32_t s_idx, const uint4 *rows) {
         source_setup(s_idx);
         uint32_t row = kNone32;
-        {
+        if constexpr (MODE == kLaneWin) {  // (srow stays a pointer: the rare tail() / near_of(0, .) paths read through it)
+            const uint32_t r = a->lane_reg0[src];
+            row = r == kLaneRegNone ? kNone32 : r;
+        } else {
             const uint32_t nr = min(nreg, kLaneRegs);
 #pragma unroll
             for (uint32_t r = kLaneRegs; r-- > 0;) {
@@ -1276,6 +1338,10 @@ struct LaneHub {
                 row = d == 0u ? r : row;
             }
         }
+        // the winner table stands for the regions' rows; a special source's own row has the
+        // source's walks among its candidates, which read_off then runs itself
+        wsh = row == kNone32 ? 0u : kLaneWinBits * row;
+        wnone = ts == kNone10 ? 0u : kLaneWinNone;
         row = ts != kNone10 ? nreg + ts - 1u : row;
         if (row == kNone32) {  // a plain cell of no region: cannot happen where the gate held
             push_fallback(a, counter, s_idx, kNone32);
@@ -1287,6 +1353,33 @@ struct LaneHub {
         bndm = h.y;
         blk = h.z;
         return read_off(s_idx, false);
+    }
+    // kLaneMemo, the winner table's build: cell w's word, region row r's winner at bit
+    // kLaneWinBits r.  The row's representative source stands for every source of the
+    // region: with the source's own walk left out, the candidates and their list compares
+    // see the source only as the first command's `from` cell, the same on both sides
+    // (DESIGN.md section 3a''').  kLaneWinNone for a special cell, a cell no boundary
+    // walks to, and a row with blockers.
+    __device__ __forceinline__ uint32_t win_word(uint32_t w, const uint4 *rows) {
+        const int wx = int(w % P.S) - int(P.H), wy = int(w / P.S) - int(P.H);
+        uint32_t tw, wr;
+        cell_word(w, wx, wy, tw, wr);
+        const Own wo{wx, wy, wr, kNone10, 0u};
+        uint32_t word = 0;
+#pragma unroll 1
+        for (uint32_t r = 0; r < nreg; ++r) {
+            source_setup(r);
+            R = rows + r * (lane_memo_row_words(TM) / 4u);
+            const uint4 h = R[TM];
+            done = h.x;
+            bndm = h.y;
+            blk = h.z;
+            LLab x = inf();
+            uint32_t bx = kNone32;
+            if (tw == kNone10) best_walk(false, wo, x, bx);
+            word |= ((bx == kNone32 || blk != 0) ? kLaneWinNone : bx) << (kLaneWinBits * r);
+        }
+        return word;
     }
 };
 

@@ -5,6 +5,8 @@
 // wave); hub_lane_memo_kernel is hub_lane_kernel without the own edges and the Dijkstra:
 // each lane takes its source's row and reads its destinations off it.  The host decides
 // per (grid, params) whether the rows stand for every source (lane_memo_rows, mr_host.cpp).
+// hub_lane_win_kernel then finds, once per (region row, cell), the boundary whose walk is
+// the best into the cell, and the read-off takes it from that table (lane_win_table).
 #include "mr_hub_lane.hpp"
 
 namespace mr {
@@ -23,17 +25,50 @@ __global__ __launch_bounds__(kBS, lane_waves(TM)) void hub_lane_build_kernel(con
     if (__any(have)) H.build_row(have, have ? s_idx : (n ? n - 1 : 0), s_idx < a->nreg);
 }
 
-// the memo kernel's LDS: the lane kernels' block (its pair table left out), then the rows
+// the memo kernels' LDS: the lane kernels' block (its pair table left out), then the rows
 __host__ __device__ inline uint32_t lane_memo_lds_bytes(uint32_t NS, uint32_t nreg, uint32_t TM) {
     return lane_blob_bytes(NS, nreg, TM) + (nreg + NS) * lane_memo_row_words(TM) * 4u;
 }
 
-// hub_lane_kernel's launch geometry, source order and end-of-pass bookkeeping.  Four
-// waves per SIMD: a lane holds no table, only the destination it is reading off.
+// The winner table of a gated (grid, params): a thread per cell.  Under the gate the best
+// boundary walk into a plain cell depends on the source only through its region row, so it
+// is found here once per (row, cell), by the read-off's own candidate and tie loops
+// (LaneHub::best_walk) from the row's representative source, a->src_v[r], without that
+// source's walk; hub_lane_memo_kernel then compares one boundary's walk with the source's
+// own.  a->lane_win: a word per cell; a->lane_reg0: the region row each cell lies in.
 template <uint32_t PERM, uint32_t TM>
-__global__ __launch_bounds__(kBS, 4) void hub_lane_memo_kernel(const KArgs *__restrict__ a) {
+__global__ __launch_bounds__(kBS, 4) void hub_lane_win_kernel(const KArgs *__restrict__ a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LaneHub<PERM, TM, false, kLaneMemo> H;
+    const uint32_t NS = a->p.NS, nreg = a->nreg, V = a->p.S * a->p.S;
+    uint4 *rows = reinterpret_cast<uint4 *>(smem + lane_blob_bytes(NS, nreg, TM));
+    {
+        const uint4 *g = reinterpret_cast<const uint4 *>(a->lane_memo);
+        const uint32_t n16 = (nreg + NS) * (lane_memo_row_words(TM) / 4u);
+        for (uint32_t i = threadIdx.x; i < n16; i += kBS) rows[i] = g[i];
+    }
+    lane_setup<TM, decltype(H), false>(a, smem, H);
+    const uint32_t w = blockIdx.x * kBS + threadIdx.x;
+    if (w >= V) return;
+    {  // the lowest region at distance 0, as memo_solve picks it from the cell's region row
+        const uint2 *row = reinterpret_cast<const uint2 *>(a->near) + (unsigned long long)w * nreg;
+        uint32_t reg = kLaneRegNone;
+        for (uint32_t r = min(nreg, kLaneRegs); r-- > 0;) reg = row[r].x == 0u ? r : reg;
+        a->lane_reg0[w] = uint8_t(reg);
+    }
+    a->lane_win[w] = H.win_word(w, rows);
+}
+
+// hub_lane_kernel's launch geometry, source order and end-of-pass bookkeeping.  Four
+// waves per SIMD: a lane holds no table, only the destination it is reading off.  MODE
+// kLaneMemo: every destination runs the candidates.  MODE kLaneWin: plain sources read
+// their destinations' best boundary off the winner table; the candidates stay for the
+// special sources, behind a wave-uniform branch, and keep the registers at four waves
+// (more waves per SIMD measured slower, DESIGN.md section 3a''').
+template <uint32_t PERM, uint32_t TM, uint32_t MODE>
+__global__ __launch_bounds__(kBS, 4) void hub_lane_memo_kernel(const KArgs *__restrict__ a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    LaneHub<PERM, TM, false, MODE> H;
 #ifdef MR_STAMPS
     H.lst_last = __builtin_amdgcn_s_memtime();
 #endif
@@ -77,20 +112,30 @@ __global__ __launch_bounds__(kBS, 4) void hub_lane_memo_kernel(const KArgs *__re
 
 // The gate holds where every special is reached at 0 legs under a Legs-first order (perms
 // 5 and 7).  The other orders are instantiated too, so that the gate alone decides.
-#define MR_MEMO_FN(NAME)                                                             \
-    static const void *NAME##_fn(uint32_t perm) {                                    \
+#define MR_MEMO_FN(FN, ...)                                                          \
+    static const void *FN(uint32_t perm) {                                           \
         switch (perm) {                                                              \
-            case 5: return reinterpret_cast<const void *>(&NAME<5, 22>);             \
-            case 7: return reinterpret_cast<const void *>(&NAME<7, 22>);             \
-            case 11: return reinterpret_cast<const void *>(&NAME<11, 22>);           \
-            case 15: return reinterpret_cast<const void *>(&NAME<15, 22>);           \
-            case 19: return reinterpret_cast<const void *>(&NAME<19, 22>);           \
-            case 21: return reinterpret_cast<const void *>(&NAME<21, 22>);           \
+            case 5: return reinterpret_cast<const void *>(&__VA_ARGS__(5));          \
+            case 7: return reinterpret_cast<const void *>(&__VA_ARGS__(7));          \
+            case 11: return reinterpret_cast<const void *>(&__VA_ARGS__(11));        \
+            case 15: return reinterpret_cast<const void *>(&__VA_ARGS__(15));        \
+            case 19: return reinterpret_cast<const void *>(&__VA_ARGS__(19));        \
+            case 21: return reinterpret_cast<const void *>(&__VA_ARGS__(21));        \
             default: return nullptr;                                                 \
         }                                                                            \
     }
-MR_MEMO_FN(hub_lane_build_kernel)
-MR_MEMO_FN(hub_lane_memo_kernel)
+#define MR_K_BUILD(P) hub_lane_build_kernel<P, 22>
+#define MR_K_MEMO(P) hub_lane_memo_kernel<P, 22, kLaneMemo>
+#define MR_K_READ(P) hub_lane_memo_kernel<P, 22, kLaneWin>
+#define MR_K_WIN(P) hub_lane_win_kernel<P, 22>
+MR_MEMO_FN(hub_lane_build_kernel_fn, MR_K_BUILD)
+MR_MEMO_FN(hub_lane_memo_kernel_fn, MR_K_MEMO)
+MR_MEMO_FN(hub_lane_read_kernel_fn, MR_K_READ)
+MR_MEMO_FN(hub_lane_win_kernel_fn, MR_K_WIN)
+#undef MR_K_BUILD
+#undef MR_K_MEMO
+#undef MR_K_READ
+#undef MR_K_WIN
 #undef MR_MEMO_FN
 
 uint32_t hub_lane_lds_bytes(uint32_t NS, uint32_t nreg);
@@ -111,9 +156,21 @@ hipError_t launch_lane_memo_build(const KArgs *d_args, const uint32_t perm[3], u
     return hipLaunchKernel(fn, dim3(1), dim3(kBS), args, bytes, stream);
 }
 
+// d_args: launch_lane_memo_build's arguments with the rows built, lane_win = V words and
+// lane_reg0 = V bytes to fill
+hipError_t launch_lane_win_build(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t V,
+                                 hipStream_t stream) {
+    const void *fn = hub_lane_win_kernel_fn(perm[0] * 9 + perm[1] * 3 + perm[2]);
+    if (!fn || NS + 1 > 22 || nreg > kLaneRegs || !V) return hipErrorInvalidValue;
+    void *args[] = {const_cast<KArgs **>(&d_args)};
+    return hipLaunchKernel(fn, dim3((V + kBS - 1u) / kBS), dim3(kBS), args, lane_memo_lds_bytes(NS, nreg, 22), stream);
+}
+
+// win: the arguments hold the winner table (lane_win, lane_reg0)
 hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
-                                hipStream_t stream) {
-    const void *fn = hub_lane_memo_kernel_fn(perm[0] * 9 + perm[1] * 3 + perm[2]);
+                                bool win, hipStream_t stream) {
+    const uint32_t pi = perm[0] * 9 + perm[1] * 3 + perm[2];
+    const void *fn = win ? hub_lane_read_kernel_fn(pi) : hub_lane_memo_kernel_fn(pi);
     if (!fn || NS + 1 > 22) return hipErrorInvalidValue;
     const uint32_t bytes = lane_memo_lds_bytes(NS, nreg, 22);
     const uint32_t waves = (n_lane + 63u) / 64u, blocks = (waves + 3u) / 4u;
