@@ -21,7 +21,8 @@
  *    and cell coordinates in i8 (src/index.rs:35-46, src/cell.rs:33-34), which
  *    caps the grid at odd S <= 255.  This ABI widens them to u16 so the
  *    BASELINE sizes (S = 1025, 4097) are representable; for S <= 255 every
- *    result is identical to the reference's.
+ *    result is identical to the reference's (on a transposed map layout: to
+ *    the specification stated at mr_grid_create).
  */
 #ifndef MARSHRUTKA_PF_H
 #define MARSHRUTKA_PF_H
@@ -92,7 +93,22 @@ typedef struct mr_grid mr_grid; /* opaque, immutable */
  * src/grid.rs:134-230,297-325).  n_cells must be S*S for odd S.
  * Errors: MR_ERR_INVALID_GRID for the reference's parse errors (not square,
  * Center missing / not at (0,0)) and for cell labels whose index adjacency
- * (src/pathfinder.rs:24-138) is not the geometric 4-neighbourhood. */
+ * (src/pathfinder.rs:24-138) is not the geometric 4-neighbourhood.
+ *
+ * Orientation.  Any of the eight layouts whose labels form that 4-grid is
+ * accepted.  On the standard layout (Blue at x < 0, y < 0) and its three mirror
+ * images every result is the reference's.  On the four transposed layouts the
+ * reference is not consistent with itself: MapGrid::parse fills the nearest
+ * campfires by a projection shortcut (src/grid.rs:152-225) that projects along
+ * the geometric axes but takes its "vertical" and "horizontal" neighbours by
+ * index, and there it departs from the reference's own nearest_campfire
+ * function (src/grid.rs:297-325).  The specification on a transposed layout is
+ * the reference's search over the nearest campfires that nearest_campfire
+ * gives for every cell (the direct argmin of Manhattan distance, then
+ * |x| != |y|, |x| + |y|, |x|, |y| of the campfire's position on the cells as
+ * given); results there can differ from a build of the reference that parsed
+ * the same map, and, the tie-break being geometric, from the labels of the
+ * standard layout of the same map. */
 int mr_grid_create(const mr_cell *cells, uint32_t n_cells, mr_grid **out);
 void mr_grid_destroy(mr_grid *grid);
 

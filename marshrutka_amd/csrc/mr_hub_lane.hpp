@@ -443,6 +443,7 @@ struct LaneHub {
     uint32_t *M;
     const uint2 *HT;     // LDS: the specials' cells by hash (lane_hash)
     uint32_t ht_probes;  // the longest probe sequence in HT
+    uint32_t rank_std;   // KArgs::rank_std, read once by lane_setup into a scalar register
     __device__ __forceinline__ void dump_meta() const {
         if constexpr (kRow) return;  // (the row holds the metas)
         const uint32_t l = lane_id();
@@ -904,8 +905,19 @@ struct LaneHub {
     // position) the rank is arithmetic and the entry a scan of the specials' cells in
     // LDS, so a source or destination costs no random HBM line; else the grid's
     // {sinfo, rank} record.
+    // The layout flag is tested on the scalar unit at each call.  Read as a->rank_std here,
+    // the compiler hoisted the load and the test out of hub_group_kernel's destination loop
+    // and carried the result into it as a lane mask, written by a v_cmp inside the inner
+    // loop over a batch's queries: a group that left that loop before the wave's last
+    // iteration had no bits in the mask, and where only such groups had plain destinations
+    // the wave took the closed form on a grid that has none (the 8-lane Fleetfoot kernels on
+    // every layout but the standard one: right metrics, the destination named by the rank of
+    // the standard layout's cell at its position).  The empty asm keeps the value in a
+    // scalar register and the compare after it.
     __device__ __forceinline__ void cell_word(uint32_t v, int x, int y, uint32_t &t, uint32_t &r) const {
-        if (a->rank_std) {
+        uint32_t std_layout = rank_std;
+        asm volatile("" : "+s"(std_layout));
+        if (std_layout) {
             r = std_rank(x, y, P.H);
             t = kNone10;
             const uint32_t h = lane_hash(v);
@@ -1449,6 +1461,7 @@ __device__ __forceinline__ void lane_setup(const KArgs *__restrict__ a, char *sm
     H.HT = reinterpret_cast<const uint2 *>(smem + lane_off_hash(NS, nreg, TM));
     const uint4 hdr = *reinterpret_cast<const uint4 *>(smem + lane_off_hdr(NS, nreg, TM));
     H.ht_probes = __builtin_amdgcn_readfirstlane(hdr.x);
+    H.rank_std = __builtin_amdgcn_readfirstlane(a->rank_std);
     H.hubm = __builtin_amdgcn_readfirstlane(hdr.y);
     H.c5m = __builtin_amdgcn_readfirstlane(hdr.z);
     H.regm = __builtin_amdgcn_readfirstlane(hdr.w);

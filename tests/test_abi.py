@@ -98,6 +98,9 @@ def test_grid_validation_on_host(eng):
 
 def test_rotated_layout_is_accepted(eng):
     # any orientation whose labels are consistent with the index adjacency is a valid map
+    # (grid creation only; all eight orientations are solved, device-grouped and given a region
+    # table in tests/test_gpu_irregular_maps.py, with the references pinned by
+    # tests/test_irregular_maps.py)
     m = SyntheticMap(7, campfires_per_homeland=1, seed=4)
     S = 7
     cells = m.cells()
