@@ -16,13 +16,13 @@
 #include <memory>
 #include <mutex>
 #include <chrono>
-#include <thread>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/marshrutka_pf.h"
 #include "mr_engine.hpp"
+#include "mr_label.hpp"
 #include "mr_pool.hpp"
 #include "mr_devmem.hpp"
 
@@ -94,10 +94,9 @@ hipError_t wire_fetch_device(const OutResult *res, const OutCmd *slots, const Ou
                              uint32_t wpool_cap, hipStream_t stream);
 hipError_t decode_records_device(const OutResult *res, const OutCmd *slots, const OutCmd *ovf, uint32_t novf,
                                  const uint32_t *q_id, uint32_t nrec, uint32_t nq, uint32_t mc,
-                                 const mr_cell_index *idx_rank, uint32_t V, uint32_t rgt, uint32_t soe, uint32_t shq,
-                                 uint32_t sfm, uint32_t ff, uint32_t *cnt, uint32_t *off, void *temp, size_t *temp_bytes,
-                                 mr_result *out, mr_command *pool, unsigned long long pool_cap, uint32_t *err,
-                                 hipStream_t stream);
+                                 const mr_cell_index *idx_rank, uint32_t V, CmdScale cs, uint32_t *cnt, uint32_t *off,
+                                 void *temp, size_t *temp_bytes, mr_result *out, mr_command *pool,
+                                 unsigned long long pool_cap, uint32_t *err, hipStream_t stream);
 }  // namespace mr
 
 
@@ -1041,12 +1040,10 @@ static int build_plan(const mr_grid *g, const mr_params *prm, const mr_query *qs
     else if (ord[0] == MR_SORT_TIME) p.bucket_mode = kBucketTime;
     else p.bucket_mode = (ord[1] == MR_SORT_LEGS) ? kBucketMoneyLegs : kBucketMoneyTime;
     // Fleetfoot (src/skill.rs:65-71): out-of-range levels leave the time raw
-    static const uint32_t ffn[4] = {1, 50, 100, 25}, ffd[4] = {1, 53, 109, 28};
-    uint32_t ff = prm->fleetfoot <= 3 ? prm->fleetfoot : 0;
     p.ff = prm->fleetfoot;
     hp.fleetfoot_raw = prm->fleetfoot;
-    p.ff_num = ffn[ff];
-    p.ff_den = ffd[ff];
+    p.ff_num = ff_ratio(prm->fleetfoot).num;
+    p.ff_den = ff_ratio(prm->fleetfoot).den;
     p.W = uint32_t((180ull * p.ff_num) / p.ff_den);  // floor(r*180): min StandardMove increment
     p.ff_c = 180u * p.ff_num;
     hp.ff_magic_ok = ff_magic(p.ff_c, p.ff_den, 2u * g->S + 256u, p.ff_magic, p.ff_shift);
@@ -3156,11 +3153,7 @@ extern "C" int mr_plan_device_outputs(mr_plan *pl, void **d_results, uint64_t *r
     return MR_OK;
 }
 
-// What a compact command's payload scales by (mr_engine.hpp Cmd): the caravan
-// seconds per distance unit, the scroll prices and the raw Fleetfoot level.
-struct CmdScale {
-    uint32_t rgt, soe, shq, sfm, ff;
-};
+// ---- decoding labels: the rules themselves are in mr_label.hpp ----
 static CmdScale cmd_scale(const HostPlan &hp) {
     return CmdScale{hp.p.rgt, hp.p.soe_cost, hp.p.shq_cost, hp.p.sfm_cost, hp.fleetfoot_raw};
 }
@@ -3173,75 +3166,63 @@ static CmdScale cmd_scale(const mr_params &prm) {
 // names no cell of the grid
 static bool expand_cmd(const mr_grid *g, const CmdScale &cs, const OutCmd &c, mr_command &o) {
     std::memset(&o, 0, sizeof(o));
-    uint32_t kind = c.kp >> 29, pay = c.kp & 0x1FFFFFFFu;
-    o.kind = uint8_t(kind);
-    switch (kind) {
-        case kCentral: o.time_s = int64_t(10) * pay; break;
-        case kStandard:
-            o.legs = pay;
-            o.time_s = int64_t(180) * pay;
-            o.fleetfoot = cs.ff;
-            break;
-        case kCaravan: {
-            uint32_t d = pay >> 1;
-            o.time_s = int64_t(cs.rgt) * d;
-            o.money = d * ((pay & 1u) ? 5u : 2u);
-            break;
-        }
-        case kSoE: o.money = cs.soe; break;
-        case kSHQ: o.money = cs.shq; break;
-        case kSFm: o.money = cs.sfm; break;
-        default: break;
-    }
-    if (kind > kSFm || c.from >= g->V || c.to >= g->V) return false;
+    const CmdCost x = cmd_cost(c.kp, cs);
+    o.kind = uint8_t(x.kind);
+    o.legs = x.legs;
+    o.money = x.money;
+    o.fleetfoot = x.fleetfoot;
+    o.time_s = x.time_s;
+    if (x.kind > kSFm || c.from >= g->V || c.to >= g->V) return false;
     o.from = g->idx[g->rank_inv[c.from]];  // device commands name cells by rank
     o.to = g->idx[g->rank_inv[c.to]];
     return true;
 }
 
+// The status a decode of many labels returns: MR_ERR_CAPACITY once a label's commands do
+// not fit the caller's pool (a short pool wins over every other error), otherwise the first
+// error in query order.  add() takes the queries' statuses in order (a record's own
+// MR_ERR_CAPACITY, written when the pass's overflow pool ran out, is an error like any
+// other there); merge() appends the fold of the queries that follow, decoded elsewhere.
+struct FetchStatus {
+    int32_t ret = MR_OK;
+    void add(int32_t status) { ret = ret == MR_OK ? status : ret; }
+    void short_pool() { ret = MR_ERR_CAPACITY; }
+    void merge(const FetchStatus &o) { o.ret == MR_ERR_CAPACITY ? short_pool() : add(o.ret); }
+};
+
 // Decodes compact record `o` (its max_cmds slots at `slots`, the overflow pool
 // `ovf` of novf commands) into r, its commands into pool[off..] when they fit
-// (else *ret = MR_ERR_CAPACITY).  Returns MR_OK, or MR_ERR_DEVICE for a record
-// that is not well formed (an overflow tag outside the pool, a bad cell rank).
-static int decode_record(const mr_grid *g, const CmdScale &cs, const OutResult &o, const OutCmd *slots, uint32_t mc,
-                         const OutCmd *ovf, uint64_t novf, mr_result &r, mr_command *pool, uint64_t pool_cap,
-                         uint64_t &off, int &ret) {
+// (else fs.short_pool()).  Returns null, or what is wrong with a record that is not
+// well formed (an overflow tag outside the pool, a bad cell rank): MR_ERR_DEVICE.
+static const char *decode_record(const mr_grid *g, const CmdScale &cs, const OutResult &o, const OutCmd *slots,
+                                 uint32_t mc, const OutCmd *ovf, uint64_t novf, mr_result &r, mr_command *pool,
+                                 uint64_t pool_cap, uint64_t &off, FetchStatus &fs) {
     std::memset(&r, 0, sizeof(r));
-    int status = int(o.ncmd_status >> 16) - 16;
+    const int st = rec_status(o);
     r.legs = o.legs;
     r.money = o.money;
     r.time_s = int64_t(o.time);
-    r.n_commands = o.ncmd_status & 0xFFFFu;
-    r.status = status;
+    r.n_commands = st == MR_NOT_FOUND ? 0u : rec_ncmd(o);
+    r.status = st;
     r.command_offset = uint32_t(off);
-    if (status == MR_NOT_FOUND) {
-        r.n_commands = 0;
-        return MR_OK;
+    if (st == MR_NOT_FOUND) return nullptr;
+    const OutCmd *src;
+    uint32_t n;
+    if (rec_source(o, slots, mc, ovf, novf, src, n) == RecSource::malformed)
+        return st == int(kStatusOverflow) ? "overflow pool record" : "record longer than its command slots";
+    if (st == int(kStatusOverflow)) r.status = MR_OK;  // (a long label is a label)
+    if (r.status != MR_OK) {
+        fs.add(r.status);
+        return nullptr;
     }
-    // a long label: its commands are in the overflow pool at {offset, count}
-    const OutCmd *src = slots;
-    if (status == int(kStatusOverflow)) {
-        const OutCmd &tag = slots[0];
-        if (!mc || tag.kp != kOvfTag || tag.to != r.n_commands || uint64_t(tag.from) + tag.to > novf)
-            return fail(MR_ERR_DEVICE, "overflow pool record");
-        src = &ovf[tag.from];
-        status = MR_OK;
-        r.status = MR_OK;
-    } else if (status == MR_OK && r.n_commands > mc) {
-        return fail(MR_ERR_DEVICE, "record longer than its command slots");
-    }
-    if (status != MR_OK) {
-        if (ret == MR_OK) ret = status;
-        return MR_OK;
-    }
-    if (off + r.n_commands <= pool_cap && pool) {
-        for (uint32_t j = 0; j < r.n_commands; ++j)
-            if (!expand_cmd(g, cs, src[j], pool[off + j])) return fail(MR_ERR_DEVICE, "command names no cell");
+    if (off + n <= pool_cap && pool) {
+        for (uint32_t j = 0; j < n; ++j)
+            if (!expand_cmd(g, cs, src[j], pool[off + j])) return "command names no cell";
     } else {
-        ret = MR_ERR_CAPACITY;
+        fs.short_pool();
     }
-    off += r.n_commands;
-    return MR_OK;
+    off += n;
+    return nullptr;
 }
 
 static int check_device_errors(mr_plan *pl, uint32_t &flags, uint32_t *ctr_out = nullptr) {
@@ -3329,11 +3310,20 @@ static int plan_collect(mr_plan *pl, std::vector<OutResult> &res, std::vector<Ou
     return MR_OK;
 }
 
-// the commands record k adds to the output pool (decode_record's `off` step)
-static uint32_t record_cmds(const OutResult &o) {
-    const int status = int(o.ncmd_status >> 16) - 16;
-    return (status == MR_OK || status == int(kStatusOverflow)) ? (o.ncmd_status & 0xFFFFu) : 0u;
-}
+// The status of a query before its record is looked at: MR_ERR_INVALID_INDEX for a query
+// that has none, else MR_OK.  Device-grouped plans keep the sorted list of such queries,
+// the others a status per query; of(i) is asked for ascending i from `first` on.
+struct QueryStatus {
+    const HostPlan &hp;
+    std::vector<uint32_t>::const_iterator inv;
+    QueryStatus(const HostPlan &h, uint32_t first) : hp(h), inv(std::lower_bound(h.invalid.begin(), h.invalid.end(), first)) {}
+    int32_t of(uint32_t i) {
+        if (!hp.dev_grouped) return hp.q_status[i];
+        if (inv == hp.invalid.end() || *inv != i) return MR_OK;
+        ++inv;
+        return MR_ERR_INVALID_INDEX;
+    }
+};
 
 // the grid's CellIndex-by-rank table on the plan's device (uploaded once)
 static const mr_cell_index *grid_idx_rank(const mr_grid *g, int dev) {
@@ -3365,8 +3355,8 @@ static bool plan_fetch_device(mr_plan *pl, mr_result *results, mr_command *pool,
     const uint64_t bound = uint64_t(nrec) * mc + nov, pcap = std::min<uint64_t>(pool_cap, std::max<uint64_t>(bound, 1));
     const CmdScale cs = cmd_scale(hp);
     size_t temp_bytes = 0;
-    (void)decode_records_device(nullptr, nullptr, nullptr, 0, nullptr, 0, nq, mc, nullptr, 0, 0, 0, 0, 0, 0, nullptr,
-                                nullptr, nullptr, &temp_bytes, nullptr, nullptr, 0, nullptr, pl->stream.get());
+    (void)decode_records_device(nullptr, nullptr, nullptr, 0, nullptr, 0, nq, mc, nullptr, 0, cs, nullptr, nullptr, nullptr,
+                                &temp_bytes, nullptr, nullptr, 0, nullptr, pl->stream.get());
     DevBuf<char> scratch_buf;
     DevBuf<mr_result> out_buf;
     DevBuf<mr_command> pool_buf;
@@ -3379,7 +3369,7 @@ static bool plan_fetch_device(mr_plan *pl, mr_result *results, mr_command *pool,
     uint32_t *err = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + 2 * cnt_b);
     void *temp = static_cast<char *>(scratch) + 2 * cnt_b + tail;
     hipError_t e = decode_records_device(pl->ka.out_res, pl->ka.out_cmd, pl->ka.ovf, nov, pl->batch.qi, nrec, nq, mc, idx_rank,
-                                         pl->grid->V, cs.rgt, cs.soe, cs.shq, cs.sfm, cs.ff, cnt, off, temp, &temp_bytes,
+                                         pl->grid->V, cs, cnt, off, temp, &temp_bytes,
                                          static_cast<mr_result *>(d_out), static_cast<mr_command *>(d_pool), pcap, err,
                                          pl->stream.get());
     uint32_t tailw[3] = {0, 0, 0};  // err, off and count of the last query: the commands written
@@ -3396,54 +3386,43 @@ static bool plan_fetch_device(mr_plan *pl, mr_result *results, mr_command *pool,
                               {pool, d_pool, fits ? size_t(total) * sizeof(mr_command) : 0}};
         e = copy_d2h(sg, 2, pl->stream.get());
     }
-    // queries without a record (an invalid index), and the status to return: the first
-    // error in query order, or MR_ERR_CAPACITY once a label's commands do not fit the
-    // caller's pool (written up to the first such label), as the host decoder does; per
-    // part of the queries on the host pool, combined in order
+    // queries without a record (an invalid index), and the status to return (FetchStatus;
+    // the commands are written up to the first label that does not fit the caller's pool,
+    // as the host decoder does); per part of the queries on the host pool, combined in order
     uint64_t end = total;
-    ret = MR_OK;
+    FetchStatus fs;
     if (e == hipSuccess && !(tailw[0] & 1u)) {
         HostPool &hpool = HostPool::get();
         const uint32_t parts = nq >= 65536u ? hpool.size() : 1u;
         std::vector<uint64_t> p_end(parts, total);
-        std::vector<int32_t> p_ret(parts, MR_OK);
+        std::vector<FetchStatus> p_fs(parts);
         hpool.run(parts, [&](uint32_t pt) {
-            uint64_t en = total;
-            int32_t rt = MR_OK;
             const uint32_t i0 = chunk_lo(nq, parts, pt);
-            // (device-grouped plans: the invalid queries from their sorted list)
-            auto inv = std::lower_bound(hp.invalid.begin(), hp.invalid.end(), i0);
+            QueryStatus qstat(hp, i0);
+            uint64_t en = total;
+            FetchStatus f;
             for (uint32_t i = i0, ie = chunk_lo(nq, parts, pt + 1); i < ie; ++i) {
                 mr_result &r = results[i];
-                int32_t qs = MR_OK;
-                if (hp.dev_grouped) {
-                    if (inv != hp.invalid.end() && *inv == i) {
-                        qs = MR_ERR_INVALID_INDEX;
-                        ++inv;
-                    }
-                } else {
-                    qs = hp.q_status[i];
-                }
-                if (qs != MR_OK) {
+                if (const int32_t qs = qstat.of(i)) {
                     std::memset(&r, 0, sizeof(r));
                     r.status = qs;
                 }
                 if (r.status == MR_OK && uint64_t(r.command_offset) + r.n_commands > pool_cap) {
                     en = std::min<uint64_t>(en, r.command_offset);
-                    rt = MR_ERR_CAPACITY;  // (the host decoder's rule: a short pool wins over other errors)
-                } else if (rt == MR_OK && r.status != MR_OK) {
-                    rt = r.status;
+                    f.short_pool();
+                } else {
+                    f.add(r.status);
                 }
             }
             p_end[pt] = en;
-            p_ret[pt] = rt;
+            p_fs[pt] = f;
         });
         for (uint32_t pt = 0; pt < parts; ++pt) {
             end = std::min(end, p_end[pt]);
-            if (p_ret[pt] == MR_ERR_CAPACITY) ret = MR_ERR_CAPACITY;
-            else if (ret == MR_OK) ret = p_ret[pt];
+            fs.merge(p_fs[pt]);
         }
     }
+    ret = fs.ret;
     const uint64_t ncopy = std::min<uint64_t>(end, pcap);
     if (e == hipSuccess && !fits && ncopy && !(tailw[0] & 1u)) {
         const D2HSeg sg{pool, d_pool, size_t(ncopy) * sizeof(mr_command)};
@@ -3480,67 +3459,51 @@ extern "C" int mr_plan_fetch(mr_plan *pl, mr_result *results, mr_command *pool, 
     const double tm1 = timing_on() ? now_ms() : 0.0;
     const HostPlan &hp = pl->hp;
     const CmdScale cs = cmd_scale(hp);
-    const uint32_t mc = hp.p.max_cmds;
-    uint64_t off = 0;
-    int ret = MR_OK;
-    // Large batches decode on host threads: each query's pool offset is the prefix sum
-    // of the commands before it, so chunks write disjoint pool ranges; the first error
-    // status in query order is the one returned, as in the serial loop below.
-    const uint32_t nthr = std::min<uint32_t>(16, std::max(1u, std::thread::hardware_concurrency() / 2));
-    if (hp.nq >= 65536 && nthr > 1 && pool) {
-        std::vector<uint64_t> first(hp.nq + 1, 0);
-        for (uint32_t i = 0; i < hp.nq; ++i)
-            first[i + 1] = first[i] + (hp.q_status[i] == MR_OK ? record_cmds(res[hp.q_pos[i]]) : 0u);
-        if (first[hp.nq] <= pool_cap) {
-            std::vector<int> rets(nthr, MR_OK), errs(nthr, MR_OK);
-            std::vector<std::string> msgs(nthr);
-            std::vector<std::thread> th;
-            const uint32_t chunk = (hp.nq + nthr - 1) / nthr;
-            for (uint32_t t = 0; t < nthr; ++t)
-                th.emplace_back([&, t]() {
-                    const uint32_t a = t * chunk, b = std::min(hp.nq, a + chunk);
-                    uint64_t o = first[std::min(a, hp.nq)];
-                    for (uint32_t i = a; i < b; ++i) {
-                        mr_result &r = results[i];
-                        if (hp.q_status[i] != MR_OK) {
-                            std::memset(&r, 0, sizeof(r));
-                            r.status = hp.q_status[i];
-                            if (rets[t] == MR_OK) rets[t] = hp.q_status[i];
-                            continue;
-                        }
-                        const uint32_t k = hp.q_pos[i];
-                        if (int e = decode_record(pl->grid, cs, res[k], mc ? &cmd[size_t(k) * mc] : nullptr, mc, ovf.data(),
-                                                  ovf.size(), r, pool, pool_cap, o, rets[t])) {
-                            errs[t] = e;
-                            msgs[t] = g_last_error;  // (thread-local)
-                            return;
-                        }
-                    }
-                });
-            for (auto &x : th) x.join();
-            for (uint32_t t = 0; t < nthr; ++t)
-                if (errs[t] != MR_OK) return fail(errs[t], msgs[t]);
-            for (uint32_t t = 0; t < nthr && ret == MR_OK; ++t) ret = rets[t];
-            if (timing_on())
-                std::fprintf(stderr, "MR_TIMING fetch n=%u: collect %.2f ms, decode %.2f ms (%u threads)\n", hp.nq, tm1 - tm0,
-                             now_ms() - tm1, nthr);
-            return ret;
-        }
+    const uint32_t nq = hp.nq, mc = hp.p.max_cmds;
+    // Large batches decode on the host pool: a query's pool offset is the count of the
+    // commands before it, so the parts write disjoint pool ranges.  Only when every command
+    // fits the caller's pool: a short pool is written up to the first label that does not
+    // fit, which one part finds as it goes.
+    HostPool &hpool = HostPool::get();
+    uint32_t parts = nq >= 65536u && pool ? hpool.size() : 1u;
+    std::vector<uint64_t> p_off(parts + 1, 0);  // the parts' first commands
+    for (uint32_t pt = 0, i = 0; parts > 1 && pt < parts; ++pt) {
+        p_off[pt + 1] = p_off[pt];
+        for (const uint32_t ie = chunk_lo(nq, parts, pt + 1); i < ie; ++i)
+            if (hp.q_status[i] == MR_OK) p_off[pt + 1] += rec_pool_cmds(res[hp.q_pos[i]]);
     }
-    for (uint32_t i = 0; i < hp.nq; ++i) {
-        mr_result &r = results[i];
-        if (hp.q_status[i] != MR_OK) {
-            std::memset(&r, 0, sizeof(r));
-            r.status = hp.q_status[i];
-            if (ret == MR_OK) ret = hp.q_status[i];
-            continue;
+    if (p_off[parts] > pool_cap) parts = 1;
+    std::vector<FetchStatus> p_fs(parts);
+    std::vector<const char *> p_bad(parts, nullptr);  // (a malformed record ends its part)
+    hpool.run(parts, [&](uint32_t pt) {
+        const uint32_t i0 = chunk_lo(nq, parts, pt);
+        QueryStatus qstat(hp, i0);
+        uint64_t off = p_off[pt];
+        FetchStatus f;
+        for (uint32_t i = i0, ie = chunk_lo(nq, parts, pt + 1); i < ie && !p_bad[pt]; ++i) {
+            mr_result &r = results[i];
+            if (const int32_t qs = qstat.of(i)) {
+                std::memset(&r, 0, sizeof(r));
+                r.status = qs;
+                f.add(qs);
+                continue;
+            }
+            const uint32_t k = hp.q_pos[i];  // records are in grouped (by source) order
+            p_bad[pt] = decode_record(pl->grid, cs, res[k], mc ? &cmd[size_t(k) * mc] : nullptr, mc, ovf.data(), ovf.size(), r,
+                                      pool, pool_cap, off, f);
         }
-        const uint32_t k = hp.q_pos[i];  // records are in grouped (by source) order
-        if ((st = decode_record(pl->grid, cs, res[k], mc ? &cmd[size_t(k) * mc] : nullptr, mc, ovf.data(), ovf.size(), r,
-                                pool, pool_cap, off, ret)))
-            return st;
+        p_fs[pt] = f;
+    });
+    FetchStatus fs;
+    for (uint32_t pt = 0; pt < parts; ++pt) {
+        if (p_bad[pt]) return fail(MR_ERR_DEVICE, p_bad[pt]);
+        // (several parts: every label fits, so a part's MR_ERR_CAPACITY is a record's own status)
+        fs.add(p_fs[pt].ret);
     }
-    return ret;
+    if (timing_on())
+        std::fprintf(stderr, "MR_TIMING fetch n=%u: collect %.2f ms, decode %.2f ms (%u threads)\n", nq, tm1 - tm0,
+                     now_ms() - tm1, parts);
+    return fs.ret;
 }
 
 extern "C" int mr_decode_records(const mr_grid *g, const mr_params *prm, const void *results, const void *commands,
@@ -3552,12 +3515,12 @@ extern "C" int mr_decode_records(const mr_grid *g, const mr_params *prm, const v
     const OutResult *res = static_cast<const OutResult *>(results);
     const OutCmd *cmd = static_cast<const OutCmd *>(commands), *ovf = static_cast<const OutCmd *>(overflow);
     uint64_t off = 0;
-    int ret = MR_OK;
+    FetchStatus fs;
     for (uint32_t k = 0; k < n; ++k)
-        if (int st = decode_record(g, cs, res[k], cmd ? cmd + size_t(k) * max_cmds : nullptr, max_cmds, ovf, overflow_n,
-                                   out[k], pool, pool_cap, off, ret))
-            return st;
-    return ret;
+        if (const char *bad = decode_record(g, cs, res[k], cmd ? cmd + size_t(k) * max_cmds : nullptr, max_cmds, ovf,
+                                            overflow_n, out[k], pool, pool_cap, off, fs))
+            return fail(MR_ERR_DEVICE, bad);
+    return fs.ret;
 }
 
 extern "C" uint32_t mr_wire_row_bytes(uint32_t max_cmds) { return 4u + 8u * max_cmds; }
@@ -3593,72 +3556,54 @@ extern "C" int mr_plan_wire_records(mr_plan *pl, void *d_rows, void *d_pool, uin
     return MR_OK;
 }
 
-// Metrics of a label from its commands (the reference's TotalCost sums, src/cost.rs:299-313;
-// a StandardMove run's time is its Fleetfoot ceil, src/skill.rs:21-30).
+// Metrics of a label from its wire commands (label_time_add: the sums the wire leaves out).
 static void wire_metrics(const CmdScale &cs, const uint32_t *cmd, uint32_t n, mr_result &r) {
-    static const uint32_t ffn[4] = {1, 50, 100, 25}, ffd[4] = {1, 53, 109, 28};
-    const uint32_t ff = cs.ff <= 3 ? cs.ff : 0;
+    const FfRatio ratio = ff_ratio(cs.ff);
     uint64_t legs = 0, money = 0, t = 0;
     for (uint32_t j = 0; j < n; ++j) {
-        const uint32_t kind = cmd[2 * j] >> 29, pay = cmd[2 * j] & 0x1FFFFFFFu;
-        switch (kind) {
-            case kCentral: t += uint64_t(10) * pay; break;
-            case kStandard:
-                legs += pay;
-                t += (uint64_t(180) * pay * ffn[ff] + ffd[ff] - 1) / ffd[ff];
-                break;
-            case kCaravan:
-                t += uint64_t(cs.rgt) * (pay >> 1);
-                money += uint64_t(pay >> 1) * ((pay & 1u) ? 5u : 2u);
-                break;
-            case kSoE: money += cs.soe; break;
-            case kSHQ: money += cs.shq; break;
-            case kSFm: money += cs.sfm; break;
-            default: break;
-        }
+        const CmdCost c = cmd_cost(cmd[2 * j], cs);
+        legs += c.legs;
+        money += c.money;
+        t += label_time_add(c, ratio);
     }
     r.legs = uint32_t(legs);
     r.money = uint32_t(money);
     r.time_s = int64_t(t);
 }
 
+static const char *wire_bad_text(WireHead h) {
+    return h == WireHead::bad_pool ? "wire pool record" : "wire record longer than its command slots";
+}
+
 // Decodes wire row `row` (max_cmds mc, the pool wp of pool_n commands) into r, its commands
-// into cmds[off..] when they fit cmd_cap (else *ret = MR_ERR_CAPACITY).  MR_OK, or
-// MR_ERR_DEVICE for a row that is not well formed.
-static int decode_wire_row(const mr_grid *g, const CmdScale &cs, const uint32_t *row, uint32_t mc, const uint32_t *wp,
-                           uint64_t pool_n, mr_result &r, mr_command *cmds, uint64_t cmd_cap, uint64_t &off, int &ret) {
+// into cmds[off..] when they fit cmd_cap (else fs.short_pool()).  Returns null, or what is
+// wrong with a row that is not well formed: MR_ERR_DEVICE.
+static const char *decode_wire_row(const mr_grid *g, const CmdScale &cs, const uint32_t *row, uint32_t mc,
+                                   const uint32_t *wp, uint64_t pool_n, mr_result &r, mr_command *cmds, uint64_t cmd_cap,
+                                   uint64_t &off, FetchStatus &fs) {
     std::memset(&r, 0, sizeof(r));
     r.command_offset = uint32_t(off);
-    const uint32_t code = row[0] >> kWireRankBits;
-    uint32_t from = row[0] & kWireRankMask, nc = 0;
-    const uint32_t *src = row + 1;
-    if (code >= kWireStatus) {
-        r.status = int32_t(code) - int32_t(kWireStatus) - 32;
-        if (r.status != MR_NOT_FOUND && ret == MR_OK) ret = r.status;
-        return MR_OK;
+    uint32_t from, nc;
+    const uint32_t *src;
+    const WireHead h = wire_head(row, mc, wp, pool_n, from, src, nc, r.status);
+    if (h == WireHead::status) {
+        if (r.status != MR_NOT_FOUND) fs.add(r.status);
+        return nullptr;
     }
-    if (code == kWireOvf) {
-        if (!mc || uint64_t(row[1]) + row[2] > pool_n) return fail(MR_ERR_DEVICE, "wire pool record");
-        src = wp + 2ull * row[1];
-        nc = row[2];
-    } else {
-        if (code > mc) return fail(MR_ERR_DEVICE, "wire record longer than its command slots");
-        nc = code;
-    }
-    r.status = MR_OK;
+    if (h != WireHead::label) return wire_bad_text(h);
     r.n_commands = nc;
     wire_metrics(cs, src, nc, r);
     if (cmds && off + nc <= cmd_cap) {
         for (uint32_t j = 0; j < nc; ++j) {
             const OutCmd c{src[2 * j], from, src[2 * j + 1], 0u};
-            if (!expand_cmd(g, cs, c, cmds[off + j])) return fail(MR_ERR_DEVICE, "command names no cell");
+            if (!expand_cmd(g, cs, c, cmds[off + j])) return "command names no cell";
             from = c.to;
         }
     } else {
-        ret = MR_ERR_CAPACITY;
+        fs.short_pool();
     }
     off += nc;
-    return MR_OK;
+    return nullptr;
 }
 
 extern "C" int mr_decode_wire(const mr_grid *g, const mr_params *prm, const void *rows, uint32_t n, uint32_t max_cmds,
@@ -3668,11 +3613,11 @@ extern "C" int mr_decode_wire(const mr_grid *g, const mr_params *prm, const void
     const uint32_t rw = 1u + 2u * max_cmds;
     const uint32_t *w = static_cast<const uint32_t *>(rows), *wp = static_cast<const uint32_t *>(pool);
     uint64_t off = 0;
-    int ret = MR_OK;
+    FetchStatus fs;
     for (uint32_t k = 0; k < n; ++k)
-        if (int st = decode_wire_row(g, cs, w + size_t(k) * rw, max_cmds, wp, pool_n, out[k], cmds, cmd_cap, off, ret))
-            return st;
-    return ret;
+        if (const char *bad = decode_wire_row(g, cs, w + size_t(k) * rw, max_cmds, wp, pool_n, out[k], cmds, cmd_cap, off, fs))
+            return fail(MR_ERR_DEVICE, bad);
+    return fs.ret;
 }
 
 // the grid's CellIndex-by-rank table on the host (one lookup a command instead of two)
@@ -3699,67 +3644,42 @@ static inline void nt_store(void *dst, const uint64_t *q, int n) {
 // decode_wire_row for the fetch: the same outputs, written with streaming stores (the
 // caller's arrays are written once and not read back here: no read-for-ownership of
 // their lines), cells from the rank table, a command's `from` as the previous `to`.
-// Returns MR_OK or MR_ERR_DEVICE (a row that is not well formed; *bad names it).
-static int fetch_wire_row(const uint32_t *row, uint32_t mc, const uint32_t *wp, uint64_t pool_n, const mr_cell_index *cell,
-                          uint32_t V, const CmdScale &cs, const uint32_t ffn, const uint32_t ffd, mr_result &r,
-                          mr_command *cmds, uint64_t cmd_cap, uint64_t &off, int &ret, const char *&bad) {
-    const uint32_t code = row[0] >> kWireRankBits;
-    uint32_t from = row[0] & kWireRankMask, nc = 0;
-    const uint32_t *src = row + 1;
+// One pass over the commands, so every command read is range-checked, written or not.
+// Returns null, or what is wrong with a row that is not well formed: MR_ERR_DEVICE.
+static const char *fetch_wire_row(const uint32_t *row, uint32_t mc, const uint32_t *wp, uint64_t pool_n,
+                                  const mr_cell_index *cell, uint32_t V, const CmdScale &cs, const FfRatio ratio, mr_result &r,
+                                  mr_command *cmds, uint64_t cmd_cap, uint64_t &off, FetchStatus &fs) {
+    uint32_t from, nc;
+    const uint32_t *src;
+    int32_t st;
     uint64_t q[5];
-    if (code >= kWireStatus) {
-        const int32_t st = int32_t(code) - int32_t(kWireStatus) - 32;
-        if (st != MR_NOT_FOUND && ret == MR_OK) ret = st;
+    const WireHead h = wire_head(row, mc, wp, pool_n, from, src, nc, st);
+    if (h == WireHead::status) {
+        if (st != MR_NOT_FOUND) fs.add(st);
         q[0] = q[1] = 0;
         q[2] = uint64_t(uint32_t(off)) << 32;
         q[3] = uint64_t(uint32_t(st));
         nt_store(&r, q, 4);
-        return MR_OK;
+        return nullptr;
     }
-    if (code == kWireOvf) {
-        if (!mc || uint64_t(row[1]) + row[2] > pool_n) return (bad = "wire pool record"), MR_ERR_DEVICE;
-        src = wp + 2ull * row[1];
-        nc = row[2];
-    } else {
-        if (code > mc) return (bad = "wire record longer than its command slots"), MR_ERR_DEVICE;
-        nc = code;
-    }
+    if (h != WireHead::label) return wire_bad_text(h);
     const bool put = cmds && off + nc <= cmd_cap;
-    if (!put) ret = MR_ERR_CAPACITY;
+    if (!put) fs.short_pool();
     uint64_t legs = 0, money = 0, t = 0;
-    if (nc && from >= V) return (bad = "command names no cell"), MR_ERR_DEVICE;
+    if (nc && from >= V) return "command names no cell";
     uint64_t fbits = nc ? cell_bits(cell[from]) : 0;
     for (uint32_t j = 0; j < nc; ++j) {
-        const uint32_t kp = src[2 * j], to = src[2 * j + 1], kind = kp >> 29, pay = kp & 0x1FFFFFFFu;
-        if (kind > kSFm || to >= V) return (bad = "command names no cell"), MR_ERR_DEVICE;
-        uint32_t cl = 0, cm = 0, cf = 0;
-        uint64_t ct = 0;
-        switch (kind) {
-            case kCentral: ct = uint64_t(10) * pay; break;
-            case kStandard:
-                cl = pay;
-                ct = uint64_t(180) * pay;
-                cf = cs.ff;
-                t += (ct * ffn + ffd - 1) / ffd;
-                ct = uint64_t(180) * pay;
-                break;
-            case kCaravan:
-                ct = uint64_t(cs.rgt) * (pay >> 1);
-                cm = (pay >> 1) * ((pay & 1u) ? 5u : 2u);
-                break;
-            case kSoE: cm = cs.soe; break;
-            case kSHQ: cm = cs.shq; break;
-            case kSFm: cm = cs.sfm; break;
-            default: break;
-        }
-        legs += cl;
-        money += cm;
-        if (kind != kStandard) t += ct;
+        const uint32_t to = src[2 * j + 1];
+        const CmdCost c = cmd_cost(src[2 * j], cs);
+        if (c.kind > kSFm || to >= V) return "command names no cell";
+        legs += c.legs;
+        money += c.money;
+        t += label_time_add(c, ratio);
         const uint64_t tbits = cell_bits(cell[to]);
         if (put) {
-            q[0] = uint64_t(kind) | uint64_t(cl) << 32;
-            q[1] = uint64_t(cm) | uint64_t(cf) << 32;
-            q[2] = ct;
+            q[0] = uint64_t(c.kind) | uint64_t(c.legs) << 32;
+            q[1] = uint64_t(c.money) | uint64_t(c.fleetfoot) << 32;
+            q[2] = uint64_t(c.time_s);
             q[3] = fbits;
             q[4] = tbits;
             nt_store(&cmds[off + j], q, 5);
@@ -3772,7 +3692,7 @@ static int fetch_wire_row(const uint32_t *row, uint32_t mc, const uint32_t *wp, 
     q[3] = uint64_t(uint32_t(MR_OK));
     nt_store(&r, q, 4);
     off += nc;
-    return MR_OK;
+    return nullptr;
 }
 
 // mr_plan_fetch through wire rows: the pass re-encoded on the device in query order
@@ -3832,81 +3752,57 @@ static bool plan_fetch_wire(mr_plan *pl, mr_result *results, mr_command *pool, u
     const double tm1 = timing_on() ? now_ms() : 0.0;
     HostPool &hpool = HostPool::get();
     const CmdScale cs = cmd_scale(hp);
-    static const uint32_t ffn_t[4] = {1, 50, 100, 25}, ffd_t[4] = {1, 53, 109, 28};
-    const uint32_t ffn = ffn_t[cs.ff <= 3 ? cs.ff : 0], ffd = ffd_t[cs.ff <= 3 ? cs.ff : 0];
+    const FfRatio ratio = ff_ratio(cs.ff);
     const mr_cell_index *cell = idx_of_rank(pl->grid);
     const uint32_t V = pl->grid->V;
     const uint32_t parts = nq >= 65536u ? hpool.size() : 1u;
     if (e == hipSuccess) e = hipEventSynchronize(ev[nch - 1].get());
-    // per (chunk, part): the first error status in its queries, or MR_ERR_CAPACITY
-    std::vector<int32_t> p_ret(size_t(nch) * parts, MR_OK), p_err(parts, MR_OK);
-    std::vector<const char *> p_msg(parts, nullptr);
+    // per (chunk, part): the status of its queries; per part: what is wrong with a malformed row
+    std::vector<FetchStatus> p_fs(size_t(nch) * parts);
+    std::vector<const char *> p_bad(parts, nullptr);
     std::vector<hipError_t> p_e(parts, hipSuccess);
     if (e == hipSuccess)
         hpool.run(parts, [&](uint32_t pt) {
-            for (uint32_t c = 0; c < nch; ++c) {
+            for (uint32_t c = 0; c < nch && !p_bad[pt]; ++c) {
                 if (hipError_t x = hipEventSynchronize(ev[c].get())) {
                     p_e[pt] = x;
                     break;
                 }
                 const uint32_t q0 = chunk_lo(nq, nch, c), nc = chunk_lo(nq, nch, c + 1) - q0;
                 const uint32_t i0 = q0 + chunk_lo(nc, parts, pt), i1 = q0 + chunk_lo(nc, parts, pt + 1);
-                // (device-grouped plans: the invalid queries from their sorted list)
-                auto inv = std::lower_bound(hp.invalid.begin(), hp.invalid.end(), i0);
-                int32_t rt = MR_OK;
-                for (uint32_t i = i0; i < i1; ++i) {
+                QueryStatus qstat(hp, i0);
+                FetchStatus f;
+                for (uint32_t i = i0; i < i1 && !p_bad[pt]; ++i) {
                     mr_result &r = results[i];
-                    int32_t qs = MR_OK;
-                    if (hp.dev_grouped) {
-                        if (inv != hp.invalid.end() && *inv == i) {
-                            qs = MR_ERR_INVALID_INDEX;
-                            ++inv;
-                        }
-                    } else {
-                        qs = hp.q_status[i];
-                    }
-                    if (qs != MR_OK) {
+                    if (const int32_t qs = qstat.of(i)) {
                         const uint64_t z[4] = {0, 0, 0, uint64_t(uint32_t(qs))};
                         nt_store(&r, z, 4);
-                        if (rt == MR_OK) rt = qs;
+                        f.add(qs);
                         continue;
                     }
                     const uint32_t *row = h_rows + size_t(i) * rw;
                     uint64_t o = row[rw - 1];
-                    int rr = MR_OK;
-                    const char *bad = nullptr;
-                    if (int st = fetch_wire_row(row, mc, h_pool, nov, cell, V, cs, ffn, ffd, r, pool, pool_cap, o, rr, bad)) {
-                        p_err[pt] = st;
-                        p_msg[pt] = bad;
-                        __builtin_ia32_sfence();
-                        return;
-                    }
-                    if (rr == MR_ERR_CAPACITY) rt = MR_ERR_CAPACITY;  // (a short pool wins over other errors)
-                    else if (rt == MR_OK && rr != MR_OK) rt = rr;
+                    FetchStatus rs;  // (the row's own: its MR_ERR_CAPACITY wins like a short pool)
+                    p_bad[pt] = fetch_wire_row(row, mc, h_pool, nov, cell, V, cs, ratio, r, pool, pool_cap, o, rs);
+                    f.merge(rs);
                 }
-                p_ret[size_t(c) * parts + pt] = rt;
+                p_fs[size_t(c) * parts + pt] = f;
             }
             __builtin_ia32_sfence();  // (the streaming stores drain before the pool's completion count)
         });
-    ret = MR_OK;
-    int32_t err = MR_OK;
-    const char *msg = nullptr;
+    const char *bad = nullptr;
     for (uint32_t pt = 0; pt < parts; ++pt) {
         if (e == hipSuccess && p_e[pt] != hipSuccess) e = p_e[pt];
-        if (err == MR_OK && p_err[pt] != MR_OK) {
-            err = p_err[pt];
-            msg = p_msg[pt];
-        }
+        if (!bad) bad = p_bad[pt];
     }
-    for (int32_t x : p_ret) {  // (chunk-major, part-minor: query order)
-        if (x == MR_ERR_CAPACITY) ret = MR_ERR_CAPACITY;
-        else if (ret == MR_OK) ret = x;
-    }
+    FetchStatus fs;
+    for (const FetchStatus &f : p_fs) fs.merge(f);  // (chunk-major, part-minor: query order)
+    ret = fs.ret;
     // the device block goes back to the cache on return, and the cache hands it out with
     // no implicit sync
     (void)hipStreamSynchronize(pl->stream.get());
     if (e != hipSuccess) return (ret = fail(MR_ERR_DEVICE, std::string("wire fetch: ") + hipGetErrorString(e))), true;
-    if (err != MR_OK) return (ret = fail(err, msg ? msg : "wire row")), true;
+    if (bad) return (ret = fail(MR_ERR_DEVICE, bad)), true;
     if (timing_on())
         std::fprintf(stderr, "MR_TIMING fetch n=%u (wire, %u chunks, %u parts): enqueue %.2f ms, copies + host decode %.2f ms\n",
                      nq, nch, parts, tm1 - tm0, now_ms() - tm1);

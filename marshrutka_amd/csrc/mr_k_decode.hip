@@ -8,92 +8,59 @@
 
 #include "../../include/marshrutka_pf.h"
 #include "mr_engine.hpp"
+#include "mr_label.hpp"
 
 namespace mr {
-
-// the record's command count as the pool counts it (0: no commands to write)
-__device__ __forceinline__ uint32_t rec_cmds(const OutResult &o) {
-    const int st = int(o.ncmd_status >> 16) - 16;
-    return (st == MR_OK || st == int(kStatusOverflow)) ? (o.ncmd_status & 0xFFFFu) : 0u;
-}
 
 __global__ void decode_count_kernel(const OutResult *__restrict__ res, const uint32_t *__restrict__ q_id, uint32_t nrec,
                                     uint32_t *__restrict__ cnt) {
     for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < nrec; k += gridDim.x * blockDim.x)
-        cnt[q_id[k]] = rec_cmds(res[k]);
+        cnt[q_id[k]] = rec_pool_cmds(res[k]);
 }
-
-struct DecodeScale {
-    uint32_t rgt, soe, shq, sfm, ff;
-};
 
 // one thread per record: its mr_result at its query, its commands at the query's offset
 // when they fit pool_cap (else the capacity flag); err bit 0: a malformed record
 __global__ void decode_write_kernel(const OutResult *__restrict__ res, const OutCmd *__restrict__ slots,
                                     const OutCmd *__restrict__ ovf, uint32_t novf, const uint32_t *__restrict__ q_id,
                                     uint32_t nrec, uint32_t mc, const uint32_t *__restrict__ off,
-                                    const mr_cell_index *__restrict__ idx_rank, uint32_t V, DecodeScale cs,
+                                    const mr_cell_index *__restrict__ idx_rank, uint32_t V, CmdScale cs,
                                     mr_result *__restrict__ out, mr_command *__restrict__ pool, unsigned long long pool_cap,
                                     uint32_t *__restrict__ err) {
     for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < nrec; k += gridDim.x * blockDim.x) {
         const OutResult o = res[k];
         const uint32_t q = q_id[k];
-        int status = int(o.ncmd_status >> 16) - 16;
+        const int st = rec_status(o);
         mr_result r;
         r.legs = o.legs;
         r.money = o.money;
         r.time_s = int64_t(o.time);
-        r.n_commands = o.ncmd_status & 0xFFFFu;
+        r.n_commands = st == MR_NOT_FOUND ? 0u : rec_ncmd(o);
         r.command_offset = off[q];
         r.reserved = 0;
-        const OutCmd *src = slots + (unsigned long long)k * mc;
-        if (status == MR_NOT_FOUND) r.n_commands = 0;
-        if (status == int(kStatusOverflow)) {  // its commands in the overflow pool at {offset, count}
-            const OutCmd tag = src[0];
-            if (!mc || tag.kp != kOvfTag || tag.to != r.n_commands || (unsigned long long)tag.from + tag.to > novf) {
-                atomicOr(err, 1u);
-                r.n_commands = 0;
-            }
-            src = ovf + tag.from;
-            status = MR_OK;
-        } else if (status == MR_OK && r.n_commands > mc) {
+        const OutCmd *src;
+        uint32_t n;
+        if (rec_source(o, slots + (unsigned long long)k * mc, mc, ovf, novf, src, n) == RecSource::malformed) {
             atomicOr(err, 1u);
-            r.n_commands = 0;  // its slots hold no more than mc commands: read none (decode_record)
+            r.n_commands = 0;  // read none of its commands
         }
-        r.status = status;
+        r.status = st == int(kStatusOverflow) ? MR_OK : st;  // (a long label is a label)
         out[q] = r;
-        if (status != MR_OK) continue;
+        if (r.status != MR_OK) continue;
         if ((unsigned long long)r.command_offset + r.n_commands > pool_cap) {
             atomicOr(err, 2u);
             continue;
         }
         for (uint32_t j = 0; j < r.n_commands; ++j) {
             const OutCmd c = src[j];
-            const uint32_t kind = c.kp >> 29, pay = c.kp & 0x1FFFFFFFu;
+            const CmdCost x = cmd_cost(c.kp, cs);
             mr_command m;
-            m.kind = uint8_t(kind);
+            m.kind = uint8_t(x.kind);
             m.reserved[0] = m.reserved[1] = m.reserved[2] = 0;
-            m.legs = 0;
-            m.money = 0;
-            m.fleetfoot = 0;
-            m.time_s = 0;
-            switch (kind) {
-                case kCentral: m.time_s = int64_t(10) * pay; break;
-                case kStandard:
-                    m.legs = pay;
-                    m.time_s = int64_t(180) * pay;
-                    m.fleetfoot = cs.ff;
-                    break;
-                case kCaravan:
-                    m.time_s = int64_t(cs.rgt) * (pay >> 1);
-                    m.money = (pay >> 1) * ((pay & 1u) ? 5u : 2u);
-                    break;
-                case kSoE: m.money = cs.soe; break;
-                case kSHQ: m.money = cs.shq; break;
-                case kSFm: m.money = cs.sfm; break;
-                default: break;
-            }
-            if (kind > kSFm || c.from >= V || c.to >= V) {
+            m.legs = x.legs;
+            m.money = x.money;
+            m.fleetfoot = x.fleetfoot;
+            m.time_s = x.time_s;
+            if (x.kind > kSFm || c.from >= V || c.to >= V) {
                 atomicOr(err, 1u);
                 continue;
             }
@@ -109,10 +76,9 @@ __global__ void decode_write_kernel(const OutResult *__restrict__ res, const Out
 // (a null temp returns the size needed).  err: one word.
 hipError_t decode_records_device(const OutResult *res, const OutCmd *slots, const OutCmd *ovf, uint32_t novf,
                                  const uint32_t *q_id, uint32_t nrec, uint32_t nq, uint32_t mc,
-                                 const mr_cell_index *idx_rank, uint32_t V, uint32_t rgt, uint32_t soe, uint32_t shq,
-                                 uint32_t sfm, uint32_t ff, uint32_t *cnt, uint32_t *off, void *temp, size_t *temp_bytes,
-                                 mr_result *out, mr_command *pool, unsigned long long pool_cap, uint32_t *err,
-                                 hipStream_t stream) {
+                                 const mr_cell_index *idx_rank, uint32_t V, CmdScale cs, uint32_t *cnt, uint32_t *off,
+                                 void *temp, size_t *temp_bytes, mr_result *out, mr_command *pool,
+                                 unsigned long long pool_cap, uint32_t *err, hipStream_t stream) {
     if (!temp) return hipcub::DeviceScan::ExclusiveSum(nullptr, *temp_bytes, cnt, off, int(nq), stream);
     hipError_t e = hipMemsetAsync(cnt, 0, size_t(nq) * 4, stream);
     if (e == hipSuccess) e = hipMemsetAsync(err, 0, 4, stream);
@@ -121,7 +87,6 @@ hipError_t decode_records_device(const OutResult *res, const OutCmd *slots, cons
         hipLaunchKernelGGL(decode_count_kernel, dim3(blocks), dim3(256), 0, stream, res, q_id, nrec, cnt);
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(temp, *temp_bytes, cnt, off, int(nq), stream);
-    const DecodeScale cs{rgt, soe, shq, sfm, ff};
     if (e == hipSuccess && nrec)
         hipLaunchKernelGGL(decode_write_kernel, dim3(blocks), dim3(256), 0, stream, res, slots, ovf, novf, q_id, nrec, mc,
                            off, idx_rank, V, cs, out, pool, pool_cap, err);
@@ -158,26 +123,28 @@ __global__ void wire_kernel(const OutResult *__restrict__ res, const OutCmd *__r
         } else {
             // rows past the records (queries with an invalid cell index) read MR_ERR_INVALID_INDEX
             const OutResult o = k < nrec ? res[k] : OutResult{0u, 0u, 0u, uint32_t(16 + MR_ERR_INVALID_INDEX) << 16};
-            const int st = int(o.ncmd_status >> 16) - 16;
-            const uint32_t n = o.ncmd_status & 0xFFFFu;
-            const OutCmd *src = slots + (unsigned long long)k * mc;
+            const int st = rec_status(o);
+            const OutCmd *const src = slots + (unsigned long long)k * mc, *cmds;
+            uint32_t n;
+            const RecSource where = rec_source(o, src, mc, ovf, nov, cmds, n);
             uint32_t *row = stage ? wsh + tid * rw : rows + (unsigned long long)(q_id ? q_id[k] : k) * rw;
             uint32_t hdr, s0 = 0, s1 = 0;
             bool copy = false;
-            if (st == MR_OK && n <= mc && n < kWireOvf) {
+            if (st == MR_OK && where == RecSource::slots && n < kWireOvf) {
                 hdr = (n ? (src[0].from & kWireRankMask) : 0u) | (n << kWireRankBits);
                 copy = true;
             } else if (st == int(kStatusOverflow) && mc) {
-                const OutCmd tag = src[0];
-                if (tag.kp == kOvfTag && tag.to == n && (unsigned long long)tag.from + n <= nov &&
-                    (unsigned long long)tag.from + n <= wpool_cap && n) {
-                    hdr = (ovf[tag.from].from & kWireRankMask) | (kWireOvf << kWireRankBits);
-                    s0 = tag.from;
+                // (a tag that is malformed, an empty label and one past the wire pool's capacity
+                // all read MR_ERR_CAPACITY here)
+                const uint32_t from = where == RecSource::pool ? uint32_t(cmds - ovf) : 0u;
+                if (where == RecSource::pool && (unsigned long long)from + n <= wpool_cap && n) {
+                    hdr = (cmds[0].from & kWireRankMask) | (kWireOvf << kWireRankBits);
+                    s0 = from;
                     s1 = n;
                     for (uint32_t j = 0; j < n; ++j) {
-                        const OutCmd c = ovf[tag.from + j];
-                        wpool[2ull * (tag.from + j)] = c.kp;
-                        wpool[2ull * (tag.from + j) + 1] = c.to;
+                        const OutCmd c = cmds[j];
+                        wpool[2ull * (from + j)] = c.kp;
+                        wpool[2ull * (from + j) + 1] = c.to;
                     }
                 } else {
                     hdr = (kWireStatus + 32u + uint32_t(MR_ERR_CAPACITY)) << kWireRankBits;
@@ -263,12 +230,12 @@ constexpr uint32_t kOrdBS = 1024;
 // record k's overflow segment {from, len} (false: not an overflow record, or a malformed tag)
 __device__ __forceinline__ bool ovf_segment(const KArgs *__restrict__ a, uint32_t k, uint32_t nov, uint32_t &from,
                                             uint32_t &len) {
-    const OutResult o = a->out_res[k];
-    if (int(o.ncmd_status >> 16) - 16 != int(kStatusOverflow)) return false;
-    const OutCmd tag = a->out_cmd[(unsigned long long)k * a->p.max_cmds];
-    len = o.ncmd_status & 0xFFFFu;
-    from = tag.from;
-    return tag.kp == kOvfTag && tag.to == len && (unsigned long long)from + len <= nov;
+    const OutCmd *src;
+    if (rec_source(a->out_res[k], a->out_cmd + (unsigned long long)k * a->p.max_cmds, a->p.max_cmds, a->ovf, nov, src,
+                   len) != RecSource::pool)
+        return false;
+    from = uint32_t(src - a->ovf);
+    return true;
 }
 
 __global__ __launch_bounds__(kOrdBS) void ovf_order_kernel(const KArgs *__restrict__ a, uint32_t nrec,

@@ -18,7 +18,10 @@
 #include <string>
 #include <vector>
 
+#include <hip/hip_runtime.h>  // (mr_engine.hpp's vector types)
+
 #include "../../include/marshrutka_pf.h"
+#include "mr_label.hpp"  // ff_ratio
 
 namespace {
 
@@ -46,16 +49,13 @@ std::string duration(int64_t s) {
 
 extern "C" int64_t mr_command_time(const mr_command *c) {
     if (!c) return 0;
-    static const int64_t num[4] = {1, 50, 100, 25}, den[4] = {1, 53, 109, 28};
     switch (c->kind) {
         case MR_CMD_CENTRAL:
         case MR_CMD_CARAVAN: return c->time_s;
-        case MR_CMD_STANDARD:
-            if (c->fleetfoot >= 1 && c->fleetfoot <= 3 && c->time_s >= 0) {
-                const int64_t n = num[c->fleetfoot], d = den[c->fleetfoot];
-                return (c->time_s * n + d - 1) / d;
-            }
-            return c->time_s;
+        case MR_CMD_STANDARD: {
+            const mr::FfRatio r = mr::ff_ratio(c->fleetfoot);  // (1 / 1 outside levels 1..3)
+            return c->time_s >= 0 ? (c->time_s * r.num + r.den - 1) / r.den : c->time_s;
+        }
         default: return 0;
     }
 }

@@ -220,6 +220,106 @@ def test_decode_wire_matches_decode_records(eng, ff, rg):
     assert bytes(memoryview(a_pool)[:ncmd]) == bytes(memoryview(b_pool)[:ncmd])
 
 
+def _decode_raw(eng, which, g, p, a, b, n, mc, cap):
+    """mr_decode_records (a, b: result records and command slots; c: overflow pool) or
+    mr_decode_wire (a: rows; c: wire pool) straight through the C ABI with a command pool of
+    `cap` entries: (returned status, mr_last_error text, the n results' fields, the pool)."""
+    import numpy as np
+    from marshrutka_amd.abi import mr_command, mr_result
+    out, pool = (mr_result * max(n, 1))(), (mr_command * max(cap, 1))()
+    prm = p.to_c()
+    arr = [np.ascontiguousarray(x, dtype=np.uint32) for x in (a, *b)]
+    ptr = [x.ctypes.data if x.size else None for x in arr]
+    if which == "records":
+        st = eng.lib().mr_decode_records(g.handle, C.byref(prm), ptr[0], ptr[1], n, mc, ptr[2], arr[2].size // 4, out,
+                                         pool, cap)
+    else:
+        st = eng.lib().mr_decode_wire(g.handle, C.byref(prm), ptr[0], n, mc, ptr[1], arr[1].size // 2, out, pool, cap)
+    res = [(r.legs, r.money, r.time_s, r.n_commands, r.command_offset, r.status) for r in out[:n]]
+    return st, (eng.last_error() if st < 0 else ""), res, pool
+
+
+@pytest.fixture(scope="module")
+def kat7(eng):
+    """The 7-square map, max_cmds 2 and SURVEY 8c KAT7's two caravans, as compact commands,
+    as wire commands and as the mr_commands they expand to."""
+    from marshrutka_amd.abi import GREEN
+    m = SyntheticMap(7, campfires_per_homeland=1, seed=4)
+    rk = _ranks(m)
+    b33, c, g33 = CellIndex.homeland(BLUE, 3, 3), CellIndex.center(), CellIndex.homeland(GREEN, 3, 3)
+    car = lambda d, five: (3 << 29) | (d << 1) | five  # noqa: E731
+    cmd4 = [[car(6, 0), rk[b33], rk[c], 0], [car(6, 1), rk[c], rk[g33], 0]]
+    full = [(3, 0, 12, 0, 1440, b33, c), (3, 0, 30, 0, 1440, c, g33)]
+    return eng.MapGrid(m.cells()), Params(route_guru=0), rk[b33], cmd4, full
+
+
+def _commands(pool, lo, hi):
+    return [(c.kind, c.legs, c.money, c.fleetfoot, c.time_s, CellIndex.from_c(c.from_), CellIndex.from_c(c.to))
+            for c in pool[lo:hi]]
+
+
+def test_decoders_malformed_command_and_short_pool(eng, kat7):
+    """A record whose second command names cell 49 of 49, after a well-formed record.  Both
+    host decoders check a command only where they write it: with a pool of 3 commands the
+    second record does not fit, nothing of it is read, and the status is MR_ERR_CAPACITY (-4),
+    not MR_ERR_DEVICE; the wire decoder still sums the row's metrics.  With room for it the
+    command is found: MR_ERR_DEVICE, "command names no cell", the commands before it written."""
+    import numpy as np
+    g, p, first, cmd4, full = kat7
+    bad = [cmd4[0], [cmd4[1][0], cmd4[1][1], 49, 0]]
+    res = np.array([[0, 42, 2880, (16 << 16) | 2], [0, 42, 2880, (16 << 16) | 2]], dtype=np.uint32)
+    slots = np.array([cmd4, bad], dtype=np.uint32)
+    rows = np.array([[first | 2 << 25, cmd4[0][0], cmd4[0][2], cmd4[1][0], cmd4[1][2]],
+                     [first | 2 << 25, bad[0][0], bad[0][2], bad[1][0], bad[1][2]]], dtype=np.uint32)
+    none = np.zeros(0, dtype=np.uint32)
+    want = [(0, 42, 2880, 2, 0, 0), (0, 42, 2880, 2, 2, 0)]
+    for which, a, b in (("records", res, (slots, none)), ("wire", rows, (none,))):
+        st, msg, out, pool = _decode_raw(eng, which, g, p, a, b, 2, 2, 3)
+        assert (st, out) == (abi.MR_ERR_CAPACITY, want), which
+        assert _commands(pool, 0, 2) == full and bytes(pool[2]) == bytes(40), which
+        st, msg, out, pool = _decode_raw(eng, which, g, p, a, b, 2, 2, 4)
+        assert (st, msg) == (abi.MR_ERR_DEVICE, "command names no cell"), which
+        assert _commands(pool, 0, 3) == full + full[:1], which
+
+
+def test_decoders_overflow_tag_at_max_cmds_0(eng, kat7):
+    """max_cmds 0 leaves no slot for an overflow tag: a record (or wire row) that claims its
+    commands are in the pool is malformed, whatever the pool holds."""
+    import numpy as np
+    g, p, first, cmd4, _ = kat7
+    res = np.array([[0, 42, 2880, ((16 + 64) << 16) | 2]], dtype=np.uint32)
+    ovf = np.array(cmd4, dtype=np.uint32)
+    st, msg, _, _ = _decode_raw(eng, "records", g, p, res, (np.zeros(0, dtype=np.uint32), ovf), 1, 0, 4)
+    assert (st, msg) == (abi.MR_ERR_DEVICE, "overflow pool record")
+    rows = np.array([[first | 64 << 25]], dtype=np.uint32)
+    st, msg, _, _ = _decode_raw(eng, "wire", g, p, rows, (ovf[:, [0, 2]],), 1, 0, 4)
+    assert (st, msg) == (abi.MR_ERR_DEVICE, "wire pool record")
+
+
+def test_decoders_status_rows_among_labels(eng, kat7):
+    """Status rows before, between and after labels: a status row's command_offset is the
+    count of the commands before it (0 for the first row), a NOT_FOUND row is no error, a
+    compact record of another status keeps its command count (a wire row carries none), and
+    the status returned is the first error in row order."""
+    import numpy as np
+    g, p, first, cmd4, full = kat7
+    res = np.array([[0, 0, 0, 17 << 16 | 9], [0, 42, 2880, (16 << 16) | 2], [7, 8, 9, (16 - 4) << 16 | 5],
+                    [0, 42, 2880, (16 << 16) | 2], [0, 0, 0, (16 - 3) << 16]], dtype=np.uint32)
+    slots = np.zeros((5, 2, 4), dtype=np.uint32)
+    slots[1] = slots[3] = cmd4
+    st_row = lambda s_: [(65 + 32 + s_) << 25, 0, 0, 0, 0]  # noqa: E731
+    lab = [first | 2 << 25, cmd4[0][0], cmd4[0][2], cmd4[1][0], cmd4[1][2]]
+    rows = np.array([st_row(1), lab, st_row(-4), lab, st_row(-3)], dtype=np.uint32)
+    none = np.zeros(0, dtype=np.uint32)
+    label = lambda off: (0, 42, 2880, 2, off, 0)  # noqa: E731
+    want = {"records": [(0, 0, 0, 0, 0, 1), label(0), (7, 8, 9, 5, 2, -4), label(2), (0, 0, 0, 0, 4, -3)],
+            "wire": [(0, 0, 0, 0, 0, 1), label(0), (0, 0, 0, 0, 2, -4), label(2), (0, 0, 0, 0, 4, -3)]}
+    for which, a, b in (("records", res, (slots, none)), ("wire", rows, (none,))):
+        st, _, out, pool = _decode_raw(eng, which, g, p, a, b, 5, 2, 4)
+        assert (st, out) == (abi.MR_ERR_CAPACITY, want[which]), which
+        assert _commands(pool, 0, 4) == full + full, which
+
+
 WIDE_PARAMS = [Params(),
                Params(fleetfoot=2, sort_by=(abi.SORT_TIME, abi.SORT_MONEY), route_guru=3, scroll_of_escape_cost=7,
                       scroll_of_escape_hq_cost=11, scroll_of_escape_forum_cost=13),

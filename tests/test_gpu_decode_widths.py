@@ -9,6 +9,9 @@ every route: the host decoder, the device decoder (pageable and page-locked arra
 wire fetch and mr_plan_wire_records + mr_decode_wire.  Each must give the crafted labels,
 and the host decoder's bytes."""
 import ctypes as C
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -221,6 +224,21 @@ def test_fetch_routes_decode_crafted_records(eng, hip, monkeypatch, mc, n, param
     finally:
         wbuf.free()
     assert not problems, "\n".join(problems)
+
+
+def test_fetch_routes_agree_past_the_parts_threshold(eng):
+    """Past 65 536 queries every fetch route splits its host work into one part per pool
+    thread and folds the parts' statuses (a short pool wins, else the first error in query
+    order).  tests/fetch_parts_child.py compares the three routes there, for both groupings
+    and for a full and a short pool, in a process of its own: the pool's thread count
+    (MR_HOST_THREADS=4) is read once per process."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("MR_HOST_DECODE", "MR_FETCH_WIRE", "MR_DEV_GROUP", "MR_GRID_STATE", "MR_ALGO")}
+    env["MR_HOST_THREADS"] = "4"
+    r = subprocess.run([sys.executable, os.path.join(here, "fetch_parts_child.py")], env=env, capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0 and "fetch parts ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 def test_wire_pool_cut(eng, oracle_lib, hip, monkeypatch):
