@@ -53,8 +53,9 @@ hipError_t launch_lane_memo_build(const KArgs *d_args, const uint32_t perm[3], u
                                   hipStream_t stream);
 hipError_t launch_lane_win_build(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t V,
                                  hipStream_t stream);
+uint32_t lane_stage_max_cmds();
 hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
-                                bool win, hipStream_t stream);
+                                bool win, bool stage, uint32_t lds_pad, hipStream_t stream);
 uint32_t hub_group_slots(uint32_t NS, uint32_t G);
 uint32_t lane_blob_build(const SpecialStatic *sp, uint32_t NS, uint32_t nreg, uint32_t TM, uint32_t rgt,
                          uint32_t ff_num, uint32_t ff_den, const uint32_t *near_sp, std::vector<uint32_t> &blob);
@@ -1656,6 +1657,8 @@ struct mr_plan {
         DevBuf<uint32_t> relist;           // lane kernel (Fleetfoot): uncertain sources for hub_kernel (KArgs::relist)
         DevBuf<uint32_t> lane_blob;        // lane / group kernels: the plan's LDS block (lane_blob_build)
         std::shared_ptr<mr_grid::LaneMemo> memo;  // lane memo rows (the grid's; ka.lane_memo when the gate holds)
+        bool lane_stage = false;    // the memo kernel stores whole command rows (kLaneStage; plan_lane_memo)
+        uint32_t lane_lds_pad = 0;  // MR_LANE_LDS_PAD: unused LDS of the memo kernel's workgroups (occupancy scans)
     } hub;
     // certified fallback (query hub plans): per slot a label table,
     // boundary ranks, source, cell words, check state and sweep list; the fill's
@@ -2599,6 +2602,22 @@ static int plan_lane_memo(mr_plan *pl) {
     }
     if (env_is("MR_LANE_WIN", "require") && !pl->ka.lane_win)
         return fail(MR_ERR_INVALID_ARG, "MR_LANE_WIN=require: " + wwhy);
+    // The stage: the read-off assembles a record's command row in LDS and the wave stores
+    // whole rows (kLaneStage), for plans of 1 .. lane_stage_max_cmds() command slots.  Off
+    // unless asked for: it writes fewer bytes and takes the same time (DESIGN.md section
+    // 3a''').  MR_LANE_STAGE=1: where the gate admits the plan; =require: plan creation
+    // fails where the staged kernel is not used; =0 or unset: never.
+    // MR_LANE_LDS_PAD (bytes): LDS the memo kernel asks for and does not use, for the
+    // occupancy scans of that section.
+    const bool stage_req = env_is("MR_LANE_STAGE", "require");
+    std::string swhy = pl->ka.lane_win ? "switched off" : "no winner table (" + wwhy + ")";
+    if (pl->ka.lane_win && (stage_req || env_is("MR_LANE_STAGE", "1"))) {
+        if (pl->hp.p.max_cmds < 1 || pl->hp.p.max_cmds > lane_stage_max_cmds())
+            swhy = "max_cmds outside 1.." + std::to_string(lane_stage_max_cmds());
+        else pl->hub.lane_stage = true;
+    }
+    if (stage_req && !pl->hub.lane_stage) return fail(MR_ERR_INVALID_ARG, "MR_LANE_STAGE=require: " + swhy);
+    if (const char *e = std::getenv("MR_LANE_LDS_PAD")) pl->hub.lane_lds_pad = uint32_t(std::strtoul(e, nullptr, 10)) & ~15u;
     return MR_OK;
 }
 
@@ -2826,7 +2845,7 @@ static hipError_t run_hub(mr_plan *pl, hipStream_t s) {
         const KArgs *la = (pl->fb_none && !big ? h.args_lane_last : h.args_lane).get();
         // (a plan whose memo gate held: the destinations only, from the grid's rows)
         if (h.lane_g) e = launch_hub_group(la, perm, NS, nreg, h.n_lane, h.lane_g, pl->hp.nonlin, s);
-        else if (pl->ka.lane_memo) e = launch_hub_lane_memo(la, perm, NS, nreg, h.n_lane, pl->ka.lane_win != nullptr, s);
+        else if (pl->ka.lane_memo) e = launch_hub_lane_memo(la, perm, NS, nreg, h.n_lane, pl->ka.lane_win != nullptr, h.lane_stage, h.lane_lds_pad, s);
         else e = launch_hub_lane(la, perm, NS, nreg, h.n_lane, pl->hp.nonlin, s);
     }
     if (e == hipSuccess && big) e = launch_hub_plan(pl, pl->fb_none ? h.args_hub_last.get() : args, s);

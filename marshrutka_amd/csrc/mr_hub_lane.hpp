@@ -291,11 +291,25 @@ __device__ __forceinline__ uint32_t ltm3(const LLab &x, const LLab &y) {
 //   kLaneMemo   destinations only: the table is the source's memo row (LDS)
 //   kLaneWin    kLaneMemo with the winner table: a plain source's destinations take their
 //               best boundary from the table instead of running the candidates
-constexpr uint32_t kLaneSolve = 0, kLaneBuild = 1, kLaneMemo = 2, kLaneWin = 3;
+//   kLaneStage  kLaneWin with the records' command rows assembled in LDS and stored whole
+//               (read_off_staged); plans of at most kLaneStageSlots command slots
+constexpr uint32_t kLaneSolve = 0, kLaneBuild = 1, kLaneMemo = 2, kLaneWin = 3, kLaneStage = 4;
+// The stage: per wave, 64 rows of kLaneStageSlots 16-byte slots, kLaneStageRow bytes apart
+// (80: sixteen lanes' 16-byte writes of one slot fall on all 64 banks).
+constexpr uint32_t kLaneStageSlots = 4, kLaneStageRow = 80, kLaneStageWave = 64u * kLaneStageRow;
 // A memo row: entry t's label at words 4 t .. 4 t + 3 (c1, c2, c3, meta; entry 0 is the
 // start label), then {done, bndm, blk, valid}.  Rows 0 .. nreg - 1 are the regions',
 // row nreg + t - 1 is special t's own (an ordinary solve from its cell).
 __host__ __device__ constexpr uint32_t lane_memo_row_words(uint32_t TM) { return 4u * TM + 4u; }
+
+// 16 bytes to / a word from global memory by address (kLaneStage).  A pointer read from
+// KArgs is generic, and a generic access also counts as an LDS one until its address is
+// resolved, so the waits of the stage's LDS traffic would stand behind the record stores.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void gstore16(void *p, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
+    *(__attribute__((address_space(1))) u32x4 *)p = u32x4{x, y, z, w};
+}
+__device__ __forceinline__ uint32_t gload32(const uint32_t *p) { return *(const __attribute__((address_space(1))) uint32_t *)p; }
 
 template <uint32_t PERM, uint32_t TM, bool NL = false, uint32_t MODE = kLaneSolve>
 struct LaneHub {
@@ -303,7 +317,8 @@ struct LaneHub {
 #ifdef MR_STAMPS
     unsigned long long lst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lst_last = 0;
 #endif
-    static constexpr bool kRow = MODE == kLaneMemo || MODE == kLaneWin;  // the table is a memo row
+    static constexpr bool kWin = MODE == kLaneWin || MODE == kLaneStage;  // destinations read the winner table
+    static constexpr bool kRow = MODE == kLaneMemo || kWin;               // the table is a memo row
     static constexpr uint32_t C1 = PERM / 9, C2 = (PERM / 3) % 3, C3 = PERM % 3;
     const KArgs *__restrict__ a;
     DevParams P;
@@ -329,7 +344,8 @@ struct LaneHub {
     // kLaneWin: the source's region in a winner word (a shift), and kLaneWinNone where the
     // source reads no winners (a special), else 0
     uint32_t wsh = 0, wnone = kLaneWinNone;
-    bool aonly = false;        // kLaneBuild: a region's row (position-independent own edges only)
+    char *STW = nullptr;  // kLaneStage: the wave's stage (LDS), lane l's row at l * kLaneStageRow
+    bool aonly = false;       // kLaneBuild: a region's row (position-independent own edges only)
 
     // ---- metrics in comparator order -------------------------------------------------
     __device__ __forceinline__ static uint32_t pick(uint32_t i, uint32_t legs, uint32_t money, uint32_t time) {
@@ -852,22 +868,50 @@ struct LaneHub {
     }
 
     // ---- output (Core::emit) --------------------------------------------------------
-    __device__ __forceinline__ void emit(const LLab x, uint32_t xid, const Own xo, uint32_t qi) const {
+    // STAGE (kLaneStage): the record's command row goes to this lane's row of the wave's
+    // stage in LDS, whole (the slots from n_commands on as zeros), and read_off_staged
+    // stores it; the result record and the overflow pool are written directly as ever.
+    // Returns whether the record has a command row (false: MR_ERR_CAPACITY).
+    // (row and oc stay two pointers, so that the stage's stores are LDS instructions)
+    template <bool STAGE>
+    __device__ __forceinline__ static void put(uint4 *row, OutCmd *oc, int i, const Cmd &c) {
+        if constexpr (STAGE) {
+            if (oc) gstore16(oc + i, c.kp, c.from, c.to, 0u);  // (the pool)
+            else row[i] = make_uint4(c.kp, c.from, c.to, 0u);
+        } else {
+            oc[i] = OutCmd{c.kp, c.from, c.to, 0};
+        }
+    }
+    template <bool STAGE>
+    __device__ __forceinline__ static void put_res(OutResult &o, uint32_t legs, uint32_t money, uint32_t time, uint32_t word) {
+        if constexpr (STAGE) gstore16(&o, legs, money, time, word);
+        else o = OutResult{legs, money, time, word};
+    }
+    template <bool STAGE = false>
+    __device__ __forceinline__ bool emit(const LLab x, uint32_t xid, const Own xo, uint32_t qi) const {
         const DevParams &p = P;
         OutResult &o = a->out_res[qi];
-        OutCmd *oc = a->out_cmd + (unsigned long long)qi * p.max_cmds;
+        uint4 *row = STAGE ? reinterpret_cast<uint4 *>(STW + lane_id() * kLaneStageRow) : nullptr;
+        OutCmd *oc = STAGE ? nullptr : a->out_cmd + (unsigned long long)qi * p.max_cmds;
         const uint32_t len = lm_len(x.m);
         const uint32_t legs = metric(x, 0), money = metric(x, 1), time = metric(x, 2);
         uint32_t status = 16;
         if (len > p.max_cmds) {  // the overflow pool, else MR_ERR_CAPACITY
             const uint32_t off = atomicAdd(counter + kCtrOvf, len);
             if (p.max_cmds == 0 || off + len > a->ovf_cap || off + len < off) {
-                o = OutResult{legs, money, time, (uint32_t(16 - 4) << 16) | (len & 0xFFFFu)};
-                return;
+                put_res<STAGE>(o, legs, money, time, (uint32_t(16 - 4) << 16) | (len & 0xFFFFu));
+                return false;
             }
-            oc[0] = OutCmd{kOvfTag, off, len, 0};
+            if constexpr (STAGE) {
+                row[0] = make_uint4(kOvfTag, off, len, 0u);
+                for (uint32_t s = 1; s < p.max_cmds; ++s) row[s] = make_uint4(0u, 0u, 0u, 0u);
+            } else {
+                oc[0] = OutCmd{kOvfTag, off, len, 0};
+            }
             oc = a->ovf + off;
             status = 16 + kStatusOverflow;
+        } else if constexpr (STAGE) {
+            for (uint32_t s = len; s < p.max_cmds; ++s) row[s] = make_uint4(0u, 0u, 0u, 0u);
         }
         int at = int(len) - 1;
         uint32_t e = x.m;
@@ -880,11 +924,11 @@ struct LaneHub {
             const Own eo{ox, oy, ork, orid, oc5};
             if (lm_nt(e) == 2 && at >= 0) {
                 const Cmd c = tail(e, eo, 1);
-                oc[at--] = OutCmd{c.kp, c.from, c.to, 0};
+                put<STAGE>(row, oc, at--, c);
             }
             if (at >= 0) {
                 const Cmd c = tail(e, eo, 0);
-                oc[at--] = OutCmd{c.kp, c.from, c.to, 0};
+                put<STAGE>(row, oc, at--, c);
             }
             eid = lm_par(e);
             if (eid == 0) break;
@@ -897,7 +941,8 @@ struct LaneHub {
             oc5 = n.c5;
         }
         if (at != -1 || eid != 0) atomicOr(counter + kCtrFlags, kErrChain);
-        o = OutResult{legs, money, time, (status << 16) | (len & 0xFFFFu)};
+        put_res<STAGE>(o, legs, money, time, (status << 16) | (len & 0xFFFFu));
+        return true;
     }
 
     // A cell's special entry (kNone10: plain) and CellIndex rank.  On a grid in the
@@ -1272,49 +1317,128 @@ struct LaneHub {
             } else {
                 w = a->q_dst[qi];
             }
-            const int wx = int(w % p.S) - int(p.H), wy = int(w / p.S) - int(p.H);
-            uint32_t tw, wr;
-            cell_word(w, wx, wy, tw, wr);
-            if (w == src) {
-                emit(st0, kOwn, Own{sx, sy, src_rk, kNone10, 0u}, qi);
-                continue;
-            }
-            if (tw != kNone10) {
-                emit(get(tw), tw, own_of(tw), qi);
-                continue;
-            }
-            const Own wo{wx, wy, wr, kNone10, 0u};
-            LLab x = inf();
-            uint32_t bx = kNone32;
-            if constexpr (MODE == kLaneWin) {
-                // the candidates only for the lanes without a winner (a special source, a cell
-                // the table leaves out): ordinary waves skip them
-                const bool slow = e == kLaneWinNone;
-                if (!slow) win_walk(e, wo, x, bx);
-                if (__any(slow)) {
-                    if (slow) best_walk(walk0, wo, x, bx);
-                }
-            } else {
-                best_walk(walk0, wo, x, bx);
-            }
-            if (bx == kNone32) {  // no boundary can walk here: cannot happen on a connected grid
-                a->out_res[qi] = OutResult{0, 0, 0, uint32_t(16 + 1) << 16};
-                continue;
-            }
-            emit(x, kOwn, wo, qi);
-            if (blk != 0) {
-                int px, py;
-                pos(bx, px, py);
-                if (!avail(bx, px, py, wx, wy)) unc = true;
-            }
-            if (NL && !unc && !(a->dbg_flags & 8u) && !walk_certain(bx, get(bx), wx, wy)) unc = true;
+            dest<false>(qi, w, e, st0, walk0, unc);
         }
-        const bool fallback = fb_sp || unc;
+        return read_off_end(s_idx, fb_sp || unc, qb - qa);
+    }
+    // Query qi of the source: its destination w (e: w's winner, kLaneWinNone without one) is
+    // the source, a special (its own label), or a plain cell (the best walk).  Returns
+    // whether the record has a command row (STAGE: in the stage, see emit).
+    template <bool STAGE>
+    __device__ __forceinline__ bool dest(uint32_t qi, uint32_t w, uint32_t e, const LLab &st0, bool walk0, bool &unc) const {
+        const DevParams &p = P;
+        const int wx = int(w % p.S) - int(p.H), wy = int(w / p.S) - int(p.H);
+        uint32_t tw, wr;
+        cell_word(w, wx, wy, tw, wr);
+        if (w == src) return emit<STAGE>(st0, kOwn, Own{sx, sy, src_rk, kNone10, 0u}, qi);
+        if (tw != kNone10) return emit<STAGE>(get(tw), tw, own_of(tw), qi);
+        const Own wo{wx, wy, wr, kNone10, 0u};
+        LLab x = inf();
+        uint32_t bx = kNone32;
+        if constexpr (kWin) {
+            // the candidates only for the lanes without a winner (a special source, a cell
+            // the table leaves out): ordinary waves skip them
+            const bool slow = e == kLaneWinNone;
+            if (!slow) win_walk(e, wo, x, bx);
+            if (__any(slow)) {
+                if (slow) best_walk(walk0, wo, x, bx);
+            }
+        } else {
+            best_walk(walk0, wo, x, bx);
+        }
+        if (bx == kNone32) {  // no boundary can walk here: cannot happen on a connected grid
+            put_res<STAGE>(a->out_res[qi], 0, 0, 0, uint32_t(16 + 1) << 16);
+            return false;
+        }
+        const bool row = emit<STAGE>(x, kOwn, wo, qi);
+        if (blk != 0) {
+            int px, py;
+            pos(bx, px, py);
+            if (!avail(bx, px, py, wx, wy)) unc = true;
+        }
+        if (NL && !unc && !(a->dbg_flags & 8u) && !walk_certain(bx, get(bx), wx, wy)) unc = true;
+        return row;
+    }
+    // kLaneStage: read_off with whole command rows (DESIGN.md section 3a''').  The wave runs
+    // the destination loop to its busiest lane's count; a lane with a query in the iteration
+    // assembles the record's row in its own row of the wave's stage (emit<true>)
+    // and marks it with the record's index; then adjacent lanes store adjacent 16 bytes of
+    // the marked rows, so a row leaves in one instruction, and where the lanes' records are
+    // consecutive (sources of one query) so do whole lines.  The stage is the wave's own:
+    // its LDS accesses execute in order, and the fences keep the compiler from moving them
+    // across the exchange.  have: the lane has a source (every lane of a wave comes here).
+    __device__ __forceinline__ uint32_t read_off_staged(bool have, uint32_t s_idx) {
+        const DevParams &p = P;
+        const LLab st0 = start();
+        uint32_t qa = 0, qb = 0;
+        if (have) {
+            qa = gload32(a->q_begin + s_idx);
+            qb = gload32(a->q_begin + s_idx + 1);
+        }
+        const bool fb_sp = a->fb_all;
+        const bool walk0 = src != p.vc;
+        const uint32_t q0 = fb_sp ? qb : qa;
+        bool unc = false;
+        uint32_t wn = 0, wwn = 0;
+        if (q0 < qb) {
+            wn = gload32(a->q_dst + q0);
+            wwn = gload32(a->lane_win + wn);
+        }
+        for (uint32_t qi = q0; __any(qi < qb); ++qi) {
+            uint32_t mark = kNone32;  // the record whose row this lane staged
+            if (qi < qb) {
+                const uint32_t w = wn, e = ((wwn >> wsh) & kLaneWinNone) | wnone;
+                if (qi + 1 < qb) {
+                    wn = gload32(a->q_dst + qi + 1);
+                    wwn = gload32(a->lane_win + wn);
+                }
+                if (dest<true>(qi, w, e, st0, walk0, unc)) mark = qi;
+            }
+            if (!__any(mark != kNone32)) continue;
+            stage_fence();
+            switch (p.max_cmds) {
+                case 1: stage_flush<1>(mark); break;
+                case 2: stage_flush<2>(mark); break;
+                case 3: stage_flush<3>(mark); break;
+                default: stage_flush<kLaneStageSlots>(mark); break;
+            }
+            stage_fence();
+        }
+        if (!have) return 0;
+        return read_off_end(s_idx, fb_sp || unc, qb - qa);
+    }
+    __device__ __forceinline__ static void stage_fence() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    // the wave's marked rows of MC slots each: 16-byte chunk c = 64 k + lane of the 64 MC is
+    // slot c % MC of lane c / MC's row, and goes to that lane's record
+    template <uint32_t MC>
+    __device__ __forceinline__ void stage_flush(uint32_t mark) const {
+        static_assert(MC >= 1 && MC <= kLaneStageSlots, "a row of the stage");
+        OutCmd *g = a->out_cmd;
+        uint32_t q[MC];
+        uint4 v[MC];
+#pragma unroll
+        for (uint32_t k = 0; k < MC; ++k) {  // (the exchange first, then the stores: no wait between them)
+            const uint32_t c = k * 64u + lane_id(), r = c / MC, s = c % MC;
+            q[k] = uint32_t(__shfl(int(mark), int(r)));
+            v[k] = reinterpret_cast<const uint4 *>(STW + r * kLaneStageRow)[s];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < MC; ++k) {
+            const uint32_t s = (k * 64u + lane_id()) % MC;
+            if (q[k] != kNone32) gstore16(g + (unsigned long long)q[k] * MC + s, v[k].x, v[k].y, v[k].z, v[k].w);
+        }
+    }
+    // the end of a source's read-off (n: its queries); returns the records written
+    __device__ __forceinline__ uint32_t read_off_end(uint32_t s_idx, bool fallback, uint32_t n) const {
         // an uncertain source goes to hub_kernel when the plan relaunches it for such
         // sources (its fallback reaches the certificate), else to the SSSP kernel
         if (fallback && a->relist && !a->fb_all) a->relist[atomicAdd(counter + kCtrRelist, 1u)] = s_idx;
         else if (fallback) push_fallback(a, counter, s_idx, kNone32);
-        return fallback ? 0u : qb - qa;
+        return fallback ? 0u : n;
     }
 
     // ---- memo rows --------------------------------------------------------------------
@@ -1336,10 +1460,11 @@ struct LaneHub {
     }
     // kLaneMemo, kLaneWin: the source's queries from its memo row (rows: the plan's rows in LDS) — a
     // special's own row, else the row of the region the source lies in (distance 0)
-    __device__ __forceinline__ uint32_t memo_solve(uint32_t s_idx, const uint4 *rows) {
+    // (kLaneStage: every lane of a wave that has a source comes here; have: this lane has one)
+    __device__ __forceinline__ uint32_t memo_solve(uint32_t s_idx, const uint4 *rows, bool have = true) {
         source_setup(s_idx);
         uint32_t row = kNone32;
-        if constexpr (MODE == kLaneWin) {  // (srow stays a pointer: the rare tail() / near_of(0, .) paths read through it)
+        if constexpr (kWin) {  // (srow stays a pointer: the rare tail() / near_of(0, .) paths read through it)
             const uint32_t r = a->lane_reg0[src];
             row = r == kLaneRegNone ? kNone32 : r;
         } else {
@@ -1356,15 +1481,18 @@ struct LaneHub {
         wnone = ts == kNone10 ? 0u : kLaneWinNone;
         row = ts != kNone10 ? nreg + ts - 1u : row;
         if (row == kNone32) {  // a plain cell of no region: cannot happen where the gate held
-            push_fallback(a, counter, s_idx, kNone32);
-            return 0;
+            if (have) push_fallback(a, counter, s_idx, kNone32);
+            if constexpr (MODE != kLaneStage) return 0;
+            have = false;  // (the lane stays for the wave's stores)
+            row = 0;
         }
         R = rows + row * (lane_memo_row_words(TM) / 4u);
         const uint4 h = R[TM];
         done = h.x;
         bndm = h.y;
         blk = h.z;
-        return read_off(s_idx, false);
+        if constexpr (MODE == kLaneStage) return read_off_staged(have, s_idx);
+        else return read_off(s_idx, false);
     }
     // kLaneMemo, the winner table's build: cell w's word, region row r's winner at bit
     // kLaneWinBits r.  The row's representative source stands for every source of the
@@ -1428,13 +1556,28 @@ __host__ __device__ inline uint32_t lane_lds_total(uint32_t NS, uint32_t nreg, u
     return lane_off_meta(NS, nreg, TM) + (kBS / 64) * TM * 64u * 4u;
 }
 
+// The memo kernels' copy of the block leaves out the pair table, its second half and the
+// row masks, which only the Dijkstra reads: the hash and the header move down by this much.
+// (MR_LANE_MEMO_HOLE: an experiment build that keeps the hole, for the A/B of DESIGN.md section 3a''')
+__host__ __device__ inline uint32_t lane_pairs_bytes(uint32_t NS, uint32_t nreg, uint32_t TM) {
+#ifdef MR_LANE_MEMO_HOLE
+    return 0u;
+#else
+    return lane_off_hash(NS, nreg, TM) - lane_off_pt(NS, nreg);
+#endif
+}
+__host__ __device__ inline uint32_t lane_memo_off_rows(uint32_t NS, uint32_t nreg, uint32_t TM) {
+    return lane_blob_bytes(NS, nreg, TM) - lane_pairs_bytes(NS, nreg, TM);
+}
+
 // The lane kernels' workgroup setup: the plan's block copied into LDS (16 B a thread per
 // step; the same block for every workgroup, so after the first ones it comes from L2),
 // and the solver's fields.
-// (PAIRS false: the pair table and its row masks, which only the Dijkstra reads, stay out)
+// (PAIRS false: the memo kernels' copy, lane_pairs_bytes shorter)
 template <uint32_t TM, class Hub, bool PAIRS = true>
 __device__ __forceinline__ void lane_setup(const KArgs *__restrict__ a, char *smem, Hub &H) {
     const uint32_t NS = a->p.NS, nreg = a->nreg;
+    const uint32_t cut = PAIRS ? 0u : lane_pairs_bytes(NS, nreg, TM);
     {
         const uint4 *blob = a->lane_blob;
         uint4 *dst = reinterpret_cast<uint4 *>(smem);
@@ -1444,7 +1587,7 @@ __device__ __forceinline__ void lane_setup(const KArgs *__restrict__ a, char *sm
         } else {
             const uint32_t p0 = lane_off_pt(NS, nreg) / 16u, p1 = lane_off_hash(NS, nreg, TM) / 16u;
             for (uint32_t i = threadIdx.x; i < p0; i += kBS) dst[i] = blob[i];
-            for (uint32_t i = p1 + threadIdx.x; i < n16; i += kBS) dst[i] = blob[i];
+            for (uint32_t i = p1 + threadIdx.x; i < n16; i += kBS) dst[i - cut / 16u] = blob[i];
         }
     }
     __syncthreads();
@@ -1452,14 +1595,21 @@ __device__ __forceinline__ void lane_setup(const KArgs *__restrict__ a, char *sm
     H.P = a->p;
     H.spl = reinterpret_cast<const SpecialStatic *>(smem);
     H.nearS = reinterpret_cast<const uint2 *>(smem + lane_off_near(NS));
-    H.PA = reinterpret_cast<const uint4 *>(smem + lane_off_pt(NS, nreg));
-    H.PB = reinterpret_cast<const uint2 *>(smem + lane_off_pb(NS, nreg, TM));
-    H.RM = reinterpret_cast<const uint32_t *>(smem + lane_off_rm(NS, nreg, TM));
-    H.M = reinterpret_cast<uint32_t *>(smem + lane_off_meta(NS, nreg, TM)) + (threadIdx.x >> 6) * (TM * 64u);
+    if constexpr (PAIRS) {
+        H.PA = reinterpret_cast<const uint4 *>(smem + lane_off_pt(NS, nreg));
+        H.PB = reinterpret_cast<const uint2 *>(smem + lane_off_pb(NS, nreg, TM));
+        H.RM = reinterpret_cast<const uint32_t *>(smem + lane_off_rm(NS, nreg, TM));
+        H.M = reinterpret_cast<uint32_t *>(smem + lane_off_meta(NS, nreg, TM)) + (threadIdx.x >> 6) * (TM * 64u);
+    } else {  // (a memo row holds the metas too)
+        H.PA = nullptr;
+        H.PB = nullptr;
+        H.RM = nullptr;
+        H.M = nullptr;
+    }
     H.mstride = 64u;
     H.mcolumn = lane_id();
-    H.HT = reinterpret_cast<const uint2 *>(smem + lane_off_hash(NS, nreg, TM));
-    const uint4 hdr = *reinterpret_cast<const uint4 *>(smem + lane_off_hdr(NS, nreg, TM));
+    H.HT = reinterpret_cast<const uint2 *>(smem + lane_off_hash(NS, nreg, TM) - cut);
+    const uint4 hdr = *reinterpret_cast<const uint4 *>(smem + lane_off_hdr(NS, nreg, TM) - cut);
     H.ht_probes = __builtin_amdgcn_readfirstlane(hdr.x);
     H.rank_std = __builtin_amdgcn_readfirstlane(a->rank_std);
     H.hubm = __builtin_amdgcn_readfirstlane(hdr.y);

@@ -25,9 +25,13 @@ __global__ __launch_bounds__(kBS, lane_waves(TM)) void hub_lane_build_kernel(con
     if (__any(have)) H.build_row(have, have ? s_idx : (n ? n - 1 : 0), s_idx < a->nreg);
 }
 
-// the memo kernels' LDS: the lane kernels' block (its pair table left out), then the rows
+// the memo kernels' LDS: the lane kernels' block without its pair table, then the rows;
+// kLaneStage: then a stage per wave
 __host__ __device__ inline uint32_t lane_memo_lds_bytes(uint32_t NS, uint32_t nreg, uint32_t TM) {
-    return lane_blob_bytes(NS, nreg, TM) + (nreg + NS) * lane_memo_row_words(TM) * 4u;
+    return lane_memo_off_rows(NS, nreg, TM) + (nreg + NS) * lane_memo_row_words(TM) * 4u;
+}
+__host__ __device__ inline uint32_t lane_stage_lds_bytes(uint32_t NS, uint32_t nreg, uint32_t TM) {
+    return lane_memo_lds_bytes(NS, nreg, TM) + (kBS / 64) * kLaneStageWave;
 }
 
 // The winner table of a gated (grid, params): a thread per cell.  Under the gate the best
@@ -41,7 +45,7 @@ __global__ __launch_bounds__(kBS, 4) void hub_lane_win_kernel(const KArgs *__res
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LaneHub<PERM, TM, false, kLaneMemo> H;
     const uint32_t NS = a->p.NS, nreg = a->nreg, V = a->p.S * a->p.S;
-    uint4 *rows = reinterpret_cast<uint4 *>(smem + lane_blob_bytes(NS, nreg, TM));
+    uint4 *rows = reinterpret_cast<uint4 *>(smem + lane_memo_off_rows(NS, nreg, TM));
     {
         const uint4 *g = reinterpret_cast<const uint4 *>(a->lane_memo);
         const uint32_t n16 = (nreg + NS) * (lane_memo_row_words(TM) / 4u);
@@ -65,15 +69,20 @@ __global__ __launch_bounds__(kBS, 4) void hub_lane_win_kernel(const KArgs *__res
 // their destinations' best boundary off the winner table; the candidates stay for the
 // special sources, behind a wave-uniform branch, and keep the registers at four waves
 // (more waves per SIMD measured slower, DESIGN.md section 3a''').
+// MODE kLaneStage: kLaneWin with whole command rows (read_off_staged); three waves per SIMD,
+// since at four the stage's few more registers would go to scratch memory.
+#ifndef MR_LANE_STAGE_WAVES
+#define MR_LANE_STAGE_WAVES 3
+#endif
 template <uint32_t PERM, uint32_t TM, uint32_t MODE>
-__global__ __launch_bounds__(kBS, 4) void hub_lane_memo_kernel(const KArgs *__restrict__ a) {
+__global__ __launch_bounds__(kBS, MODE == kLaneStage ? MR_LANE_STAGE_WAVES : 4) void hub_lane_memo_kernel(const KArgs *__restrict__ a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LaneHub<PERM, TM, false, MODE> H;
 #ifdef MR_STAMPS
     H.lst_last = __builtin_amdgcn_s_memtime();
 #endif
     const uint32_t NS = a->p.NS, nreg = a->nreg;
-    uint4 *rows = reinterpret_cast<uint4 *>(smem + lane_blob_bytes(NS, nreg, TM));
+    uint4 *rows = reinterpret_cast<uint4 *>(smem + lane_memo_off_rows(NS, nreg, TM));
     {  // (before lane_setup's barrier; L2-resident after the first workgroups)
         const uint4 *g = reinterpret_cast<const uint4 *>(a->lane_memo);
         const uint32_t n16 = (nreg + NS) * (lane_memo_row_words(TM) / 4u);
@@ -89,7 +98,14 @@ __global__ __launch_bounds__(kBS, 4) void hub_lane_memo_kernel(const KArgs *__re
 #endif
     const uint32_t s_idx = (blockIdx.x * (kBS / 64) + (threadIdx.x >> 6)) * 64u + lane_id();
     uint32_t written = 0;
-    if (s_idx < a->n_lane) written = H.memo_solve(s_idx, rows);
+    if constexpr (MODE == kLaneStage) {  // whole waves: the rows' stores are the wave's
+        H.STW = smem + lane_memo_lds_bytes(NS, nreg, TM) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kLaneStageWave;
+        const uint32_t n = a->n_lane;
+        const bool have = s_idx < n;
+        if (__any(have)) written = H.memo_solve(have ? s_idx : n - 1u, rows, have);
+    } else {
+        if (s_idx < a->n_lane) written = H.memo_solve(s_idx, rows);
+    }
 #ifdef MR_STAMPS
     {
         const unsigned long long now_ = __builtin_amdgcn_s_memtime();
@@ -128,14 +144,17 @@ __global__ __launch_bounds__(kBS, 4) void hub_lane_memo_kernel(const KArgs *__re
 #define MR_K_MEMO(P) hub_lane_memo_kernel<P, 22, kLaneMemo>
 #define MR_K_READ(P) hub_lane_memo_kernel<P, 22, kLaneWin>
 #define MR_K_WIN(P) hub_lane_win_kernel<P, 22>
+#define MR_K_STAGE(P) hub_lane_memo_kernel<P, 22, kLaneStage>
 MR_MEMO_FN(hub_lane_build_kernel_fn, MR_K_BUILD)
 MR_MEMO_FN(hub_lane_memo_kernel_fn, MR_K_MEMO)
 MR_MEMO_FN(hub_lane_read_kernel_fn, MR_K_READ)
 MR_MEMO_FN(hub_lane_win_kernel_fn, MR_K_WIN)
+MR_MEMO_FN(hub_lane_stage_kernel_fn, MR_K_STAGE)
 #undef MR_K_BUILD
 #undef MR_K_MEMO
 #undef MR_K_READ
 #undef MR_K_WIN
+#undef MR_K_STAGE
 #undef MR_MEMO_FN
 
 uint32_t hub_lane_lds_bytes(uint32_t NS, uint32_t nreg);
@@ -166,13 +185,19 @@ hipError_t launch_lane_win_build(const KArgs *d_args, const uint32_t perm[3], ui
     return hipLaunchKernel(fn, dim3((V + kBS - 1u) / kBS), dim3(kBS), args, lane_memo_lds_bytes(NS, nreg, 22), stream);
 }
 
-// win: the arguments hold the winner table (lane_win, lane_reg0)
+// the widest plan (command slots a record) the staged kernel takes
+uint32_t lane_stage_max_cmds() { return kLaneStageSlots; }
+
+// win: the arguments hold the winner table (lane_win, lane_reg0); stage: and the command
+// rows leave through the stage (max_cmds 1 .. lane_stage_max_cmds()).  lds_pad: bytes of
+// LDS the kernel does not use, which hold it to fewer workgroups a CU (occupancy scans)
 hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
-                                bool win, hipStream_t stream) {
+                                bool win, bool stage, uint32_t lds_pad, hipStream_t stream) {
     const uint32_t pi = perm[0] * 9 + perm[1] * 3 + perm[2];
-    const void *fn = win ? hub_lane_read_kernel_fn(pi) : hub_lane_memo_kernel_fn(pi);
-    if (!fn || NS + 1 > 22) return hipErrorInvalidValue;
-    const uint32_t bytes = lane_memo_lds_bytes(NS, nreg, 22);
+    const void *fn = stage ? hub_lane_stage_kernel_fn(pi) : win ? hub_lane_read_kernel_fn(pi) : hub_lane_memo_kernel_fn(pi);
+    if (!fn || NS + 1 > 22 || (stage && !win)) return hipErrorInvalidValue;
+    const uint32_t bytes = (stage ? lane_stage_lds_bytes(NS, nreg, 22) : lane_memo_lds_bytes(NS, nreg, 22)) + lds_pad;
+    if (bytes > 64u * 1024u) return hipErrorInvalidValue;
     const uint32_t waves = (n_lane + 63u) / 64u, blocks = (waves + 3u) / 4u;
     void *args[] = {const_cast<KArgs **>(&d_args)};
     return hipLaunchKernel(fn, dim3(blocks ? blocks : 1u), dim3(kBS), args, bytes, stream);
