@@ -236,6 +236,12 @@ struct KArgs {
     // candidates for every destination
     uint32_t *lane_win;
     uint8_t *lane_reg0;
+    // hub_lane_memo_kernel<.., kLaneQuery> (a record per lane): the row-major cell of record
+    // q's source, for the lane sources' records [0, nq_lane), nq_lane = q_begin[n_lane];
+    // written at plan creation from src_v / q_begin (lane_query_expand_kernel).  Null: the
+    // plan runs a source per lane
+    const uint32_t *q_srcv;
+    uint32_t nq_lane;
 };
 constexpr uint32_t kLaneWinBits = 5u, kLaneWinNone = 31u, kLaneRegNone = 255u;
 // cert_redo[slot]: kRedoFill — promoted specials: the closed form again, both checks and the

@@ -56,6 +56,10 @@ hipError_t launch_lane_win_build(const KArgs *d_args, const uint32_t perm[3], ui
 uint32_t lane_stage_max_cmds();
 hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
                                 bool win, bool stage, uint32_t lds_pad, hipStream_t stream);
+hipError_t launch_lane_query_expand(const uint32_t *src_v, const uint32_t *q_begin, uint32_t n_lane, uint32_t *q_srcv,
+                                    hipStream_t stream);
+hipError_t launch_hub_lane_query(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t nq_lane,
+                                 uint32_t grid_cap, uint32_t lds_pad, hipStream_t stream);
 uint32_t hub_group_slots(uint32_t NS, uint32_t G);
 uint32_t lane_blob_build(const SpecialStatic *sp, uint32_t NS, uint32_t nreg, uint32_t TM, uint32_t rgt,
                          uint32_t ff_num, uint32_t ff_den, const uint32_t *near_sp, std::vector<uint32_t> &blob);
@@ -242,6 +246,7 @@ struct mr_grid {
         std::vector<uint32_t> srcs;  // the rows' sources: a plain cell per region, then the specials' cells
         DevBuf<uint32_t> d_win;
         DevBuf<uint8_t> d_reg0;
+        bool blk0 = false;  // no row has a blocker: no destination can make its source uncertain
         size_t bytes() const { return d_rows.size() * 4 + d_win.size() * 4 + d_reg0.size(); }
     };
     mutable std::mutex memo_mu;
@@ -928,6 +933,7 @@ struct HostPlan {
     // stay empty until a host caller needs them (host_arrays), the counts below hold
     bool dev_grouped = false, mirrored = false;
     uint32_t nrec = 0, nsrc = 0, n_small = 0;  // valid queries, sources, sources of <= kLaneMaxQ queries
+    uint32_t nq_small = 0;                     // the queries of those sources
     std::vector<uint32_t> invalid;             // device grouping: the invalid queries, ascending
 };
 static uint32_t nrec_of(const HostPlan &hp) { return hp.dev_grouped ? hp.nrec : uint32_t(hp.q_id.size()); }
@@ -1629,6 +1635,7 @@ struct mr_plan {
         uint32_t *src = nullptr, *qb = nullptr, *qd = nullptr, *qi = nullptr;
         DevBuf<char> gscratch;   // device grouping: phase 1's scratch, until the partition (plan_partition)
         DevBuf<uint32_t> gcnt;   // device grouping: its counts
+        DevBuf<uint32_t> qsv;    // the record-per-lane memo kernel: each lane record's source cell (KArgs::q_srcv)
         void take(DevBuf<uint32_t> &&b, const size_t at[4]) {
             block = std::move(b);
             src = block.get() + at[0], qb = block.get() + at[1], qd = block.get() + at[2], qi = block.get() + at[3];
@@ -1659,6 +1666,10 @@ struct mr_plan {
         std::shared_ptr<mr_grid::LaneMemo> memo;  // lane memo rows (the grid's; ka.lane_memo when the gate holds)
         bool lane_stage = false;    // the memo kernel stores whole command rows (kLaneStage; plan_lane_memo)
         uint32_t lane_lds_pad = 0;  // MR_LANE_LDS_PAD: unused LDS of the memo kernel's workgroups (occupancy scans)
+        bool lane_query = false;    // the memo kernel takes a record per lane (kLaneQuery; plan_lane_memo)
+        bool lane_query_gate = false;  // the plan admits that kernel (lane_query: and its overflow pool does, bind_outputs)
+        uint32_t nq_lane = 0;       // the records of the lane sources, q_begin[n_lane]
+        uint32_t lane_query_grid = 0;  // MR_LANE_QUERY_GRID: at most this many workgroups (0: no cap; kNone32: one chunk a wave)
     } hub;
     // certified fallback (query hub plans): per slot a label table,
     // boundary ranks, source, cell words, check state and sweep list; the fill's
@@ -1889,8 +1900,10 @@ static std::shared_ptr<mr_grid::LaneMemo> lane_memo_rows(const mr_grid *g, int d
     const uint32_t leg[3] = {1u, 0u, 180u};
     const uint32_t w[3] = {leg[hp.p.perm[0]], leg[hp.p.perm[1]], leg[hp.p.perm[2]]};
     m->gate = true;
+    m->blk0 = true;
     for (uint32_t r = 0; r < nrows && m->gate; ++r) {
         const uint32_t *row = &rows[size_t(r) * rw];
+        if (row[rw - 2] != 0u) m->blk0 = false;  // ({done, bndm, blk, valid} end a row)
         if (row[rw - 1] != 1u) {
             m->gate = false;
             m->why = "an uncertain row (blockers)";
@@ -1912,6 +1925,9 @@ static std::shared_ptr<mr_grid::LaneMemo> lane_memo_rows(const mr_grid *g, int d
 // candidates (4097^2: 84 MB).  MR_LANE_WIN_BUDGET overrides the budget (bytes; tests force 0).
 static size_t lane_win_bytes(uint32_t V) { return size_t(V) * 5; }
 constexpr size_t kLaneWinBudget = size_t(96) << 20;
+// whether a plan the record-per-lane memo kernel admits runs it without being asked to
+// (MR_LANE_QUERY, plan_lane_memo; the A/B of DESIGN.md section 3a''')
+constexpr bool kLaneQueryDefault = true;
 // what the memos cached on one grid may hold together (a plan holds its own memo, so
 // clearing the cache frees a memo when its last plan goes)
 constexpr size_t kLaneMemoCacheBytes = size_t(256) << 20;
@@ -2116,6 +2132,7 @@ static int group_on_device(mr_plan *pl, const mr_query *qs, uint32_t n) {
     hp.nrec = cnt[0];
     hp.nsrc = cnt[1];
     hp.n_small = cnt[2];
+    hp.nq_small = cnt[3];
     const uint32_t ninv = cnt[4];
     if (ninv != n - cnt[0]) return fail(MR_ERR_DEVICE, "device grouping: inconsistent counts");
     hp.invalid.clear();
@@ -2394,6 +2411,8 @@ static void plan_base_args(mr_plan *pl, uint32_t n) {
     ka.lane_memo = nullptr;
     ka.lane_win = nullptr;
     ka.lane_reg0 = nullptr;
+    ka.q_srcv = nullptr;
+    ka.nq_lane = 0;
     ka.nreg = 0;
     ka.fb_mode = 0;
     ka.fb_all = env_fallback_all() ? 1u : 0u;  // tests cover the fallback path
@@ -2618,6 +2637,38 @@ static int plan_lane_memo(mr_plan *pl) {
     }
     if (stage_req && !pl->hub.lane_stage) return fail(MR_ERR_INVALID_ARG, "MR_LANE_STAGE=require: " + swhy);
     if (const char *e = std::getenv("MR_LANE_LDS_PAD")) pl->hub.lane_lds_pad = uint32_t(std::strtoul(e, nullptr, 10)) & ~15u;
+    // A record per lane (kLaneQuery, DESIGN.md section 3a'''): persistent waves read the lane
+    // sources' records off in record order, each record's source cell from q_srcv.  For
+    // plans on the winner table whose rows have no blockers, so that no destination can
+    // send its source to the fallback, and that do not send every source there.
+    // MR_LANE_QUERY=0: never; =1: where the gate admits the plan; =require: plan creation
+    // fails where the kernel is not used.  MR_LANE_QUERY_GRID (diagnostic): at most this
+    // many workgroups (a small plan's waves then walk several chunks); =full: a workgroup
+    // per 256 records, every wave one chunk.
+    const bool query_req = env_is("MR_LANE_QUERY", "require");
+    std::string qwhy = pl->ka.lane_win ? "switched off" : "no winner table (" + wwhy + ")";
+    if (pl->ka.lane_win && (query_req || env_is("MR_LANE_QUERY", "1") || (kLaneQueryDefault && !env_is("MR_LANE_QUERY", "0")))) {
+        mr_plan::Hub &h = pl->hub;
+        h.nq_lane = hp.dev_grouped ? hp.nq_small : hp.q_begin[h.n_lane];
+        if (h.lane_stage) qwhy = "the staged kernel was asked for (MR_LANE_STAGE)";
+        else if (pl->ka.fb_all) qwhy = "every source goes to the fallback (MR_HUB_FALLBACK_ALL)";
+        else if (!h.memo->blk0) qwhy = "a memo row with blockers";
+        else if (!h.nq_lane) qwhy = "no records";
+        else {
+            const hipStream_t ps = pl->stream.get();
+            if (pl->batch.qsv.alloc(h.nq_lane) != hipSuccess) return fail(MR_ERR_DEVICE, "hipMalloc record sources");
+            hipError_t e = launch_lane_query_expand(pl->batch.src, pl->batch.qb, h.n_lane, pl->batch.qsv.get(), ps);
+            const hipError_t es = hipStreamSynchronize(ps);
+            if (e == hipSuccess) e = es;
+            if (e != hipSuccess) return fail(MR_ERR_DEVICE, std::string("record sources: ") + hipGetErrorString(e));
+            pl->ka.q_srcv = pl->batch.qsv.get();
+            pl->ka.nq_lane = h.nq_lane;
+            h.lane_query = h.lane_query_gate = true;
+        }
+    }
+    if (query_req && !pl->hub.lane_query) return fail(MR_ERR_INVALID_ARG, "MR_LANE_QUERY=require: " + qwhy);
+    if (const char *e = std::getenv("MR_LANE_QUERY_GRID"))
+        pl->hub.lane_query_grid = !std::strcmp(e, "full") ? kNone32 : uint32_t(std::strtoul(e, nullptr, 10));
     return MR_OK;
 }
 
@@ -2845,6 +2896,7 @@ static hipError_t run_hub(mr_plan *pl, hipStream_t s) {
         const KArgs *la = (pl->fb_none && !big ? h.args_lane_last : h.args_lane).get();
         // (a plan whose memo gate held: the destinations only, from the grid's rows)
         if (h.lane_g) e = launch_hub_group(la, perm, NS, nreg, h.n_lane, h.lane_g, pl->hp.nonlin, s);
+        else if (h.lane_query) e = launch_hub_lane_query(la, perm, NS, nreg, h.nq_lane, h.lane_query_grid, h.lane_lds_pad, s);
         else if (pl->ka.lane_memo) e = launch_hub_lane_memo(la, perm, NS, nreg, h.n_lane, pl->ka.lane_win != nullptr, h.lane_stage, h.lane_lds_pad, s);
         else e = launch_hub_lane(la, perm, NS, nreg, h.n_lane, pl->hp.nonlin, s);
     }
@@ -3008,6 +3060,11 @@ extern "C" int mr_plan_bind_outputs_ex(mr_plan *pl, void *d_results, void *d_com
         pl->ka.ovf = reinterpret_cast<OutCmd *>(d_overflow);
         pl->ka.ovf_cap = overflow_cap;
         pl->out.ovf_order = true;
+        // Which labels fit a pool that is too small depends on the order in which they take
+        // their space.  A source per lane gives a source's records theirs in record order; a
+        // record per lane (kLaneQuery) does not.  A pool smaller than the plan's own is where
+        // that order decides statuses, so such a binding keeps the source-per-lane read-off.
+        pl->hub.lane_query = pl->hub.lane_query_gate && overflow_cap >= std::max<size_t>(4096, size_t(pl->hp.nq) * 8);
     }
     if (upload_args(pl) != MR_OK) return fail(MR_ERR_DEVICE, "kernel args");
     return MR_OK;

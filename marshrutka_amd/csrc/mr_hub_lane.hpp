@@ -293,7 +293,10 @@ __device__ __forceinline__ uint32_t ltm3(const LLab &x, const LLab &y) {
 //               best boundary from the table instead of running the candidates
 //   kLaneStage  kLaneWin with the records' command rows assembled in LDS and stored whole
 //               (read_off_staged); plans of at most kLaneStageSlots command slots
-constexpr uint32_t kLaneSolve = 0, kLaneBuild = 1, kLaneMemo = 2, kLaneWin = 3, kLaneStage = 4;
+//   kLaneQuery  kLaneWin with one RECORD per lane (query_record): the source's cell comes
+//               from KArgs::q_srcv, so a wave's lanes write consecutive records; for plans
+//               whose rows have no blockers (no query can make its source uncertain)
+constexpr uint32_t kLaneSolve = 0, kLaneBuild = 1, kLaneMemo = 2, kLaneWin = 3, kLaneStage = 4, kLaneQuery = 5;
 // The stage: per wave, 64 rows of kLaneStageSlots 16-byte slots, kLaneStageRow bytes apart
 // (80: sixteen lanes' 16-byte writes of one slot fall on all 64 banks).
 constexpr uint32_t kLaneStageSlots = 4, kLaneStageRow = 80, kLaneStageWave = 64u * kLaneStageRow;
@@ -310,6 +313,7 @@ __device__ __forceinline__ void gstore16(void *p, uint32_t x, uint32_t y, uint32
     *(__attribute__((address_space(1))) u32x4 *)p = u32x4{x, y, z, w};
 }
 __device__ __forceinline__ uint32_t gload32(const uint32_t *p) { return *(const __attribute__((address_space(1))) uint32_t *)p; }
+__device__ __forceinline__ uint32_t gload8(const uint8_t *p) { return *(const __attribute__((address_space(1))) uint8_t *)p; }
 
 template <uint32_t PERM, uint32_t TM, bool NL = false, uint32_t MODE = kLaneSolve>
 struct LaneHub {
@@ -317,7 +321,7 @@ struct LaneHub {
 #ifdef MR_STAMPS
     unsigned long long lst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lst_last = 0;
 #endif
-    static constexpr bool kWin = MODE == kLaneWin || MODE == kLaneStage;  // destinations read the winner table
+    static constexpr bool kWin = MODE == kLaneWin || MODE == kLaneStage || MODE == kLaneQuery;  // destinations read the winner table
     static constexpr bool kRow = MODE == kLaneMemo || kWin;               // the table is a memo row
     static constexpr uint32_t C1 = PERM / 9, C2 = (PERM / 3) % 3, C3 = PERM % 3;
     const KArgs *__restrict__ a;
@@ -982,9 +986,10 @@ struct LaneHub {
     // specials, the certification of the settled labels, the destinations.  solve() runs
     // them all; the memo kernels (mr_k_lane_memo.hip) run the first four once per region
     // and special (kLaneBuild) and the last one per source (kLaneMemo).
-    __device__ __forceinline__ void source_setup(uint32_t s_idx) {
+    __device__ __forceinline__ void source_setup(uint32_t s_idx) { source_cell(a->src_v[s_idx]); }
+    __device__ __forceinline__ void source_cell(uint32_t v) {
         const DevParams &p = P;
-        src = a->src_v[s_idx];
+        src = v;
         sx = int(src % p.S) - int(p.H);
         sy = int(src / p.S) - int(p.H);
         cell_word(src, sx, sy, ts, src_rk);
@@ -1493,6 +1498,42 @@ struct LaneHub {
         blk = h.z;
         if constexpr (MODE == kLaneStage) return read_off_staged(have, s_idx);
         else return read_off(s_idx, false);
+    }
+    // kLaneQuery: record q of the plan's grouped order, whose source lies at cell sv (r0:
+    // lane_reg0[sv]) and whose destination is w (ww: lane_win[w]).  What memo_solve derives
+    // from a source index comes from the cell and the byte here; the destination is dest's.
+    // Where the gate of this mode holds (no blockers in any row, linear run times) dest
+    // cannot make a source uncertain, so the only fallback is the plain cell of no region:
+    // every record of such a source comes here and writes nothing, and the lane with the
+    // source's first record finds its index in q_begin and hands it over once.
+    // Returns the records written (0 or 1).
+    __device__ __forceinline__ uint32_t query_record(uint32_t q, uint32_t sv, uint32_t w, uint32_t r0, uint32_t ww,
+                                                     const uint4 *rows) {
+        source_cell(sv);
+        uint32_t row = r0 == kLaneRegNone ? kNone32 : r0;
+        wsh = row == kNone32 ? 0u : kLaneWinBits * row;
+        wnone = ts == kNone10 ? 0u : kLaneWinNone;
+        row = ts != kNone10 ? nreg + ts - 1u : row;
+        if (row == kNone32) {  // a plain cell of no region: cannot happen where the memo gate held
+            if (q == 0 || gload32(a->q_srcv + q - 1) != sv) {
+                uint32_t lo = 0, hi = a->n_lane;  // q_begin[lo] <= q < q_begin[hi]
+                while (hi - lo > 1u) {
+                    const uint32_t mid = lo + (hi - lo) / 2u;
+                    if (a->q_begin[mid] <= q) lo = mid;
+                    else hi = mid;
+                }
+                push_fallback(a, counter, lo, kNone32);
+            }
+            return 0;
+        }
+        R = rows + row * (lane_memo_row_words(TM) / 4u);
+        const uint4 h = R[TM];
+        done = h.x;
+        bndm = h.y;
+        blk = h.z;
+        bool unc = false;
+        dest<false>(q, w, ((ww >> wsh) & kLaneWinNone) | wnone, start(), src != P.vc, unc);
+        return 1u;
     }
     // kLaneMemo, the winner table's build: cell w's word, region row r's winner at bit
     // kLaneWinBits r.  The row's representative source stands for every source of the

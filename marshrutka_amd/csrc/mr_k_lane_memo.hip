@@ -9,6 +9,11 @@
 // the best into the cell, and the read-off takes it from that table (lane_win_table).
 #include "mr_hub_lane.hpp"
 
+#include <algorithm>
+#include <map>
+#include <mutex>
+#include <tuple>
+
 namespace mr {
 
 // one wave: lane l solves source l of a->src_v (the first a->nreg of them region
@@ -98,7 +103,39 @@ __global__ __launch_bounds__(kBS, MODE == kLaneStage ? MR_LANE_STAGE_WAVES : 4) 
 #endif
     const uint32_t s_idx = (blockIdx.x * (kBS / 64) + (threadIdx.x >> 6)) * 64u + lane_id();
     uint32_t written = 0;
-    if constexpr (MODE == kLaneStage) {  // whole waves: the rows' stores are the wave's
+    if constexpr (MODE == kLaneQuery) {
+        // A record per lane, persistent waves: the launch's waves walk the chunks of 64
+        // records at a grid-wide stride, so the chunks in flight are neighbours in the
+        // output.  A chunk's source cells and destinations (coalesced) and then its two
+        // gathers (the source's region byte, the destination's winner word) are issued
+        // before the previous chunk's destinations are read off and stored.
+        const uint32_t nq = a->nq_lane, chunks = (nq + 63u) / 64u, nw = gridDim.x * (kBS / 64);
+        const uint32_t *qsv = a->q_srcv, *qd = a->q_dst, *win = a->lane_win;
+        const uint8_t *reg0 = a->lane_reg0;
+        uint32_t c = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBS / 64) + (threadIdx.x >> 6));
+        uint32_t q = c * 64u + lane_id(), sv = 0, w = 0, r0 = 0, ww = 0;
+        bool have = c < chunks && q < nq;
+        if (have) {
+            sv = gload32(qsv + q);
+            w = gload32(qd + q);
+            r0 = gload8(reg0 + sv);
+            ww = gload32(win + w);
+        }
+        for (; c < chunks; c += nw) {
+            const uint32_t cq = q, csv = sv, cw = w, cr0 = r0, cww = ww;
+            const bool chave = have;
+            const uint32_t cn = c + nw;
+            q = cn * 64u + lane_id();
+            have = cn < chunks && q < nq;
+            if (have) {
+                sv = gload32(qsv + q);
+                w = gload32(qd + q);
+                r0 = gload8(reg0 + sv);
+                ww = gload32(win + w);
+            }
+            if (chave) written += H.query_record(cq, csv, cw, cr0, cww, rows);
+        }
+    } else if constexpr (MODE == kLaneStage) {  // whole waves: the rows' stores are the wave's
         H.STW = smem + lane_memo_lds_bytes(NS, nreg, TM) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kLaneStageWave;
         const uint32_t n = a->n_lane;
         const bool have = s_idx < n;
@@ -145,16 +182,19 @@ __global__ __launch_bounds__(kBS, MODE == kLaneStage ? MR_LANE_STAGE_WAVES : 4) 
 #define MR_K_READ(P) hub_lane_memo_kernel<P, 22, kLaneWin>
 #define MR_K_WIN(P) hub_lane_win_kernel<P, 22>
 #define MR_K_STAGE(P) hub_lane_memo_kernel<P, 22, kLaneStage>
+#define MR_K_QUERY(P) hub_lane_memo_kernel<P, 22, kLaneQuery>
 MR_MEMO_FN(hub_lane_build_kernel_fn, MR_K_BUILD)
 MR_MEMO_FN(hub_lane_memo_kernel_fn, MR_K_MEMO)
 MR_MEMO_FN(hub_lane_read_kernel_fn, MR_K_READ)
 MR_MEMO_FN(hub_lane_win_kernel_fn, MR_K_WIN)
 MR_MEMO_FN(hub_lane_stage_kernel_fn, MR_K_STAGE)
+MR_MEMO_FN(hub_lane_query_kernel_fn, MR_K_QUERY)
 #undef MR_K_BUILD
 #undef MR_K_MEMO
 #undef MR_K_READ
 #undef MR_K_WIN
 #undef MR_K_STAGE
+#undef MR_K_QUERY
 #undef MR_MEMO_FN
 
 uint32_t hub_lane_lds_bytes(uint32_t NS, uint32_t nreg);
@@ -201,6 +241,75 @@ hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uin
     const uint32_t waves = (n_lane + 63u) / 64u, blocks = (waves + 3u) / 4u;
     void *args[] = {const_cast<KArgs **>(&d_args)};
     return hipLaunchKernel(fn, dim3(blocks ? blocks : 1u), dim3(kBS), args, bytes, stream);
+}
+
+// KArgs::q_srcv of a plan: a thread per lane source writes its cell over its records
+__global__ __launch_bounds__(kBS) void lane_query_expand_kernel(const uint32_t *__restrict__ src_v,
+                                                                const uint32_t *__restrict__ q_begin, uint32_t n_lane,
+                                                                uint32_t *__restrict__ q_srcv) {
+    const uint32_t s = blockIdx.x * kBS + threadIdx.x;
+    if (s >= n_lane) return;
+    const uint32_t v = src_v[s], qb = q_begin[s + 1];
+    for (uint32_t q = q_begin[s]; q < qb; ++q) q_srcv[q] = v;
+}
+hipError_t launch_lane_query_expand(const uint32_t *src_v, const uint32_t *q_begin, uint32_t n_lane, uint32_t *q_srcv,
+                                    hipStream_t stream) {
+    if (!n_lane) return hipSuccess;
+    hipLaunchKernelGGL(lane_query_expand_kernel, dim3((n_lane + kBS - 1u) / kBS), dim3(kBS), 0, stream, src_v, q_begin,
+                       n_lane, q_srcv);
+    return hipGetLastError();
+}
+
+// the workgroups of `fn` with `bytes` of LDS that the device holds at once (asked once per
+// (device, function, LDS size)); 0: the query failed
+static uint32_t resident_workgroups(const void *fn, uint32_t bytes) {
+    static std::mutex mu;
+    static std::map<std::tuple<int, const void *, uint32_t>, uint32_t> cache;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    std::lock_guard<std::mutex> lk(mu);
+    const auto key = std::make_tuple(dev, fn, bytes);
+    const auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, int(kBS), bytes) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return cache[key] = uint32_t(per_cu) * uint32_t(cus);
+}
+
+// hub_lane_memo_kernel<.., kLaneQuery> over the nq_lane records of the lane sources (d_args:
+// the winner table, q_srcv and nq_lane set): min(a workgroup per 256 records, the resident
+// workgroups), each wave walking chunks of 64 records at the grid's stride.  grid_cap
+// (diagnostic, MR_LANE_QUERY_GRID): at most this many workgroups, 0: no cap; kNone32: a
+// workgroup per 256 records whatever is resident (every wave takes one chunk)
+hipError_t launch_hub_lane_query(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t nq_lane,
+                                 uint32_t grid_cap, uint32_t lds_pad, hipStream_t stream) {
+    const void *fn = hub_lane_query_kernel_fn(perm[0] * 9 + perm[1] * 3 + perm[2]);
+    if (!fn || NS + 1 > 22) return hipErrorInvalidValue;
+    const uint32_t bytes = lane_memo_lds_bytes(NS, nreg, 22) + lds_pad;
+    if (bytes > 64u * 1024u) return hipErrorInvalidValue;
+    uint32_t blocks = std::max(1u, (nq_lane + kBS - 1u) / kBS);
+    if (grid_cap != kNone32) {
+        const uint32_t res = resident_workgroups(fn, bytes);
+        if (!res) return hipErrorInvalidValue;
+        blocks = std::min(blocks, res);
+        if (grid_cap) {
+            blocks = std::min(blocks, grid_cap);
+        } else {
+            // The waves take the chunks in rounds, and a round costs about the same
+            // whether its last waves have a chunk or not: the fewest workgroups that keep
+            // the round count, so that the last round is as full as the others (c4: 15 625
+            // chunks, 1 024 resident workgroups: 4 rounds either way, of 977 workgroups)
+            const uint32_t chunks = (nq_lane + 63u) / 64u, wpb = kBS / 64u;
+            const uint32_t rounds = (chunks + blocks * wpb - 1u) / (blocks * wpb);
+            blocks = std::max(1u, (chunks + rounds * wpb - 1u) / (rounds * wpb));
+        }
+    }
+    void *args[] = {const_cast<KArgs **>(&d_args)};
+    return hipLaunchKernel(fn, dim3(blocks), dim3(kBS), args, bytes, stream);
 }
 
 }  // namespace mr
