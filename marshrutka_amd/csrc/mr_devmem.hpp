@@ -153,6 +153,18 @@ inline void pstream_release(hipStream_t s) {
     p.free.emplace_back(dev, s);
 }
 
+// `bytes` of device memory cleared to zero before this returns.  hipMemset on device memory
+// only queues the fill on the null stream and returns (a 16 GiB fill: 4 us, then 2.8 ms of
+// work), and the plans' streams are non-blocking: they do not wait for the null stream.  A
+// kernel launched on one of them right afterwards could run before the fill, which then
+// wipes what the kernel counted; with other host threads' copies queued on the null stream
+// the fill can be milliseconds late.  So the fill is waited for here.
+inline hipError_t zero_now(void *p, size_t bytes) {
+    hipError_t e = hipMemsetAsync(p, 0, bytes, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    return e;
+}
+
 // ---- owners (move-only; an empty one holds nothing and releases nothing) ----
 enum class DevMem { cache, direct };  // block cache (plans, temporaries) | plain hipMalloc (grid tables)
 
@@ -184,10 +196,10 @@ public:
         p_ = static_cast<T *>(p), n_ = count, how_ = how;
         return hipSuccess;
     }
-    // allocates and clears to zero bytes
+    // allocates and clears to zero bytes (the zeros are there when it returns: zero_now)
     hipError_t alloc_zero(size_t count, DevMem how = DevMem::cache) {
         hipError_t e = alloc(count, how);
-        if (e == hipSuccess) e = hipMemset(p_, 0, count * sizeof(T));
+        if (e == hipSuccess) e = zero_now(p_, count * sizeof(T));
         return e;
     }
     void reset() {

@@ -3306,7 +3306,8 @@ static int check_device_errors(mr_plan *pl, uint32_t &flags, uint32_t *ctr_out =
     if (int st = read_counters(pl, ctr)) return st;
     if (ctr_out) std::memcpy(ctr_out, ctr, sizeof(ctr));  // (read before the flags are collected)
     flags = ctr[kCtrFlags];
-    if (flags) (void)hipMemset(pl->cur().counter.get() + kCtrFlags, 0, 4);  // collected
+    // collected (cleared before the next pass can flag again: zero_now)
+    if (flags) (void)zero_now(pl->cur().counter.get() + kCtrFlags, 4);
     // overlap plans: the other slots' counter blocks belong to earlier passes; their
     // flags and written counts are checked (and collected) as well
     for (uint32_t i = 0; i < pl->slots.size(); ++i) {
@@ -3315,7 +3316,7 @@ static int check_device_errors(mr_plan *pl, uint32_t &flags, uint32_t *ctr_out =
         uint32_t oc[kCtrWords];
         if (hipMemcpy(oc, k.counter.get(), kCtrWords * 4, hipMemcpyDeviceToHost) != hipSuccess)
             return fail(MR_ERR_DEVICE, "copy counter");
-        if (oc[kCtrFlags]) (void)hipMemset(k.counter.get() + kCtrFlags, 0, 4);
+        if (oc[kCtrFlags]) (void)zero_now(k.counter.get() + kCtrFlags, 4);
         flags |= oc[kCtrFlags];  // a fused plan's look-ahead solve may have flagged a slot not yet filled
         if (flags == 0 && k.used && oc[kCtrLastWritten] != nrec_of(pl->hp))
             return fail(MR_ERR_DEVICE, "internal: " + std::to_string(oc[kCtrLastWritten]) + " of " +
