@@ -443,6 +443,38 @@ int mr_sssp_label(mr_plan *plan, uint32_t i, mr_cell_index dst, mr_result *out, 
  * so the caller can size the pool), or an error. */
 int mr_sssp_labels(mr_plan *plan, uint32_t i, mr_result *results, mr_command *pool, uint64_t pool_cap);
 
+/* ---- cost matrices: n_src sources x n_dst destinations ------------------- */
+/* Every (source, destination) pair's label metrics as one dense table on the device:
+ * an all-destinations plan that evaluates only the listed destinations and holds no cell
+ * words.  mr_plan_run / _wait / _get_stats / _kernel_ms (the read-off kernel's time) /
+ * _destroy apply.  Sources and destinations may repeat.  A record is mr_label_record with
+ * mr_sssp_records' meaning of `via`: what that call gives for the same (source, cell); a
+ * destination equal to its source reads {0, 0, 0, 0xFFFFFFFF}.
+ * Errors: MR_ERR_INVALID_ARG for a null pointer, n_src == 0 or n_dst == 0;
+ * MR_ERR_INVALID_INDEX for a source or destination that is not a grid cell (mr_last_error
+ * names which one and its position); MR_ERR_LIMIT when plan sources x pitch x 16 B does
+ * not fit the device block cache's largest block (16 GiB); MR_ERR_NO_DEVICE as for the
+ * other plans.  The mr_sssp_* and pair-plan accessors (mr_plan_fetch,
+ * mr_plan_device_outputs, mr_plan_bind_outputs*, mr_plan_wire_records) return
+ * MR_ERR_INVALID_ARG on a matrix plan, the mr_matrix_* accessors on any other plan.
+ * MR_ERR_LIMIT for labels holds as stated at mr_status: the accessors that wait report it. */
+int mr_matrix_plan_create(const mr_grid *grid, const mr_params *params, const mr_cell_index *sources, uint32_t n_src,
+                          const mr_cell_index *dests, uint32_t n_dst, mr_plan **out);
+/* records of the caller's source i x destination j at out[i * n_dst + j] (waits);
+ * MR_ERR_CAPACITY if cap_records < n_src * n_dst */
+int mr_matrix_records(mr_plan *plan, mr_label_record *out, uint64_t cap_records);
+/* device rows: [plan source][pitch] mr_label_record, pitch = n_dst rounded up to 8
+ * records (whole 128 B lines; pad records unspecified).  Waits for the passes enqueued so
+ * far; the next mr_plan_run rewrites the rows (mr_plan_wait orders a reader on another stream) */
+int mr_matrix_device_records(mr_plan *plan, void **d_records, uint64_t *bytes);
+int mr_matrix_record_pitch(mr_plan *plan, uint32_t *records_per_row);
+/* row_of_source[i] = device row of the caller's source i (plan sources are the
+ * distinct sources in row-major cell order, as in all-destinations plans) */
+int mr_matrix_source_rows(const mr_plan *plan, uint32_t *row_of_source, uint32_t n_src);
+/* FindPath::eval(sources[i], dests[j]) rebuilt in full from record and table:
+ * MR_OK, MR_ERR_CAPACITY (out->n_commands > cap) or an error */
+int mr_matrix_label(mr_plan *plan, uint32_t i, uint32_t j, mr_result *out, mr_command *cmds, uint32_t cap);
+
 /* ---- misc ---------------------------------------------------------------- */
 uint32_t mr_abi_version(void);
 /* Human-readable description of the last error on this thread. */

@@ -221,6 +221,16 @@ extern "C" {
     pub fn mr_sssp_labels(plan: *mut mr_plan, i: u32, results: *mut mr_result, pool: *mut mr_command,
                           pool_cap: u64) -> c_int;
 
+    // cost matrices: n_src sources x n_dst destinations
+    pub fn mr_matrix_plan_create(grid: *const mr_grid, params: *const mr_params, sources: *const mr_cell_index,
+                                 n_src: u32, dests: *const mr_cell_index, n_dst: u32, out: *mut *mut mr_plan) -> c_int;
+    pub fn mr_matrix_records(plan: *mut mr_plan, out: *mut mr_label_record, cap_records: u64) -> c_int;
+    pub fn mr_matrix_device_records(plan: *mut mr_plan, d_records: *mut *mut c_void, bytes: *mut u64) -> c_int;
+    pub fn mr_matrix_record_pitch(plan: *mut mr_plan, records_per_row: *mut u32) -> c_int;
+    pub fn mr_matrix_source_rows(plan: *const mr_plan, row_of_source: *mut u32, n_src: u32) -> c_int;
+    pub fn mr_matrix_label(plan: *mut mr_plan, i: u32, j: u32, out: *mut mr_result, cmds: *mut mr_command,
+                           cap: u32) -> c_int;
+
     // misc
     pub fn mr_abi_version() -> u32;
     pub fn mr_last_error() -> *const c_char;

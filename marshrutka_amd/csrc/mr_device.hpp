@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mr_engine.hpp"
+#include "mr_label.hpp"
 
 #include <map>
 #include <mutex>
@@ -849,12 +850,52 @@ struct Core {
         emit(x, qi);
     }
     __device__ __forceinline__ void write_outputs(uint32_t s_idx) const {
+        if (a->all_mode == kAllMatrix) {
+            write_matrix(s_idx);
+            return;
+        }
         if (a->all_mode) {
             write_all(s_idx);
             return;
         }
         const uint32_t q0 = a->q_begin[s_idx], q1 = a->q_begin[s_idx + 1];
         for (uint32_t i = q0 + threadIdx.x; i < q1; i += kBS) write_output(a->q_dst[i], i);
+    }
+    // the cell word write_all stores for cell v: the settled state word's walk (b, k) as it stands
+    // (write_all keeps its own loop on purpose: the all-destinations path of the SSSP kernel
+    // stays the code it was, so its measurements carry over)
+    __device__ __forceinline__ CellWord cell_word(uint32_t v) const {
+        const uint32_t sw = ld_state(v);
+        const uint32_t t = special_of(v);
+        if (v == src) return kViaSource;
+        if (t != kNone10) return kViaSpecial | t;
+        if (!(sw & kStSettled)) flag(kErrBucket);  // every cell of the connected grid settles
+        return sw & ((kNone10 << kStBShift) | kStKMask);
+    }
+    // matrix plans: the label table and one record per listed destination, the expansion of
+    // the cell word write_all would store (pad records of the row: zeros)
+    __device__ __forceinline__ void write_matrix(uint32_t s_idx) const {
+        const DevParams &p = P;
+        const uint32_t T = p.NS + 1;
+        const unsigned long long tb = (unsigned long long)s_idx * T;
+        for (uint32_t t = threadIdx.x; t <= p.NS; t += kBS) {
+            a->out_tab[tb + t] = R[t];
+            a->out_lex[tb + t] = kNone32;
+        }
+        uint4 *row = a->mx_rows + (unsigned long long)s_idx * a->mx_pitch;
+        const FfRatio ff{p.ff_num, p.ff_den};
+        for (uint32_t j = threadIdx.x; j < a->mx_pitch; j += kBS) {
+            mr_label_record o{0u, 0u, 0u, 0u};
+            if (j < a->mx_ndst) {
+                const uint32_t xy = a->mx_dst[j].x;
+                const int x = int(short(xy & 0xFFFFu)), y = int(short(xy >> 16));
+                const uint32_t v = uint32_t(y + int(p.H)) * p.S + uint32_t(x + int(p.H));
+                if (!expand_word(cell_word(v), T, ff, [&](uint32_t t, uint32_t q) { return R[t].m[q]; }, o))
+                    flag(kErrChain);
+            }
+            row[j] = make_uint4(o.legs, o.money, o.time_s, o.via);
+        }
+        if (threadIdx.x == 0) a->src_state[s_idx] = 2;
     }
     // all-destinations mode: the label table and a cell word for every cell (CellWord:
     // the settled state word's walk (b, k) as it stands)

@@ -242,7 +242,17 @@ struct KArgs {
     // plan runs a source per lane
     const uint32_t *q_srcv;
     uint32_t nq_lane;
+    // matrix plans (all_mode == kAllMatrix, DESIGN.md section 3b'): no cell words; per source
+    // a row of mx_pitch 16 B records {legs, money, time, via}, record j the label of
+    // destination mx_dst[j] = {x | y << 16 (int16 each, geometric), kViaSpecial | t for special
+    // t, else the row-major cell}; mx_pitch = mx_ndst rounded up to 8 records (a 128 B line)
+    const uint2 *mx_dst;
+    uint4 *mx_rows;
+    uint32_t mx_ndst;
+    uint32_t mx_pitch;
 };
+// KArgs::all_mode: a cell word per (source, cell), or a record per (source, listed destination)
+constexpr uint32_t kAllCells = 1u, kAllMatrix = 2u;
 constexpr uint32_t kLaneWinBits = 5u, kLaneWinNone = 31u, kLaneRegNone = 255u;
 // cert_redo[slot]: kRedoFill — promoted specials: the closed form again, both checks and the
 // repair; kRedoSweep — specials the last check demoted: the repair from the current words

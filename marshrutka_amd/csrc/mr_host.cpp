@@ -37,6 +37,8 @@ hipError_t launch_hub(const KArgs *d_args, const uint32_t perm[3], uint32_t spw,
 hipError_t launch_fill(const KArgs *d_args, const uint32_t perm[3], uint32_t gx, uint32_t gy, hipStream_t stream);
 int hub_blocks_per_cu(const uint32_t perm[3], uint32_t spw, bool nonlin, uint32_t bytes);
 int fill_blocks_per_cu(const uint32_t perm[3]);
+hipError_t launch_matrix(const KArgs *d_args, const uint32_t perm[3], uint32_t gx, hipStream_t stream);
+int matrix_blocks_per_cu(const uint32_t perm[3]);
 hipError_t launch_hub_fill(const KArgs *hub_args, const KArgs *fill_args, const uint32_t perm[3], uint32_t spw,
                            uint32_t hub_blocks, uint32_t fill_blocks, uint32_t lds_bytes, hipStream_t stream);
 int hub_fill_blocks_per_cu(const uint32_t perm[3], uint32_t spw, uint32_t lds_bytes);
@@ -1589,6 +1591,9 @@ struct mr_plan {
     KArgs ka{};  // all but the per-pass fields, which slot_args() fills from a slot
     int device = 0;
     bool all_mode = false;
+    // a matrix plan: an all-destinations plan (all_mode) that writes a record per listed
+    // destination (Matrix below) instead of a cell word per cell
+    bool matrix = false;
     bool grid_in_lds = false;
     uint32_t algo = kAlgoGeneric;
     uint32_t blocks = 0, cus = 256;
@@ -1653,6 +1658,14 @@ struct mr_plan {
         DevBuf<uint32_t> ws;               // the SSSP kernel's HBM slots
         DevBuf<unsigned long long> dbg;    // diagnostic builds: per-workgroup phase cycles
     } out;
+    // matrix plans: the destinations as the kernels read them (KArgs::mx_dst), their cells
+    // on the host, and the record rows (KArgs::mx_rows: [plan source][pitch])
+    struct Matrix {
+        DevBuf<uint2> dst;
+        DevBuf<uint4> rows;
+        std::vector<uint32_t> dst_v;
+        uint32_t n_src = 0, n_dst = 0, pitch = 0, per_cu = 1;
+    } mx;
     struct Hub {
         uint32_t n_lane = 0;               // sources on the lane kernel; the rest on hub_kernel
         uint32_t lane_g = 0;               // > 0: the n_lane sources run G lanes each (hub_group_kernel)
@@ -2435,15 +2448,53 @@ static int plan_all_outputs(mr_plan *pl, uint32_t n) {
         if (std::atoi(e) == 64) align = 64;
     const uint32_t pitch = (hp.p.S + align - 1) / align * align;
     ka.rec_pitch = pitch;
-    if (pl->out.rec.alloc(ns * hp.p.S * pitch) != hipSuccess || k.tab.alloc(ns * T) != hipSuccess ||
+    // (a matrix plan holds no cell words: its rows are plan_matrix_outputs')
+    if ((!pl->matrix && pl->out.rec.alloc(ns * hp.p.S * pitch) != hipSuccess) || k.tab.alloc(ns * T) != hipSuccess ||
         k.lex.alloc(ns * T) != hipSuccess || k.sstate.alloc(ns) != hipSuccess)
         return fail(MR_ERR_DEVICE, "hipMalloc all-destinations outputs");
-    ka.all_mode = 1;
+    ka.all_mode = pl->matrix ? kAllMatrix : kAllCells;
     ka.out_rec = pl->out.rec.get();
     ka.early_exit_max = 0;  // every cell must settle
     pl->src_of_input.assign(n, kNone32);
     for (uint32_t si = 0; si < ka.nsrc; ++si)
         for (uint32_t q = hp.q_begin[si]; q < hp.q_begin[si + 1]; ++q) pl->src_of_input[hp.q_id[q]] = si;
+    return MR_OK;
+}
+
+// The largest block the device block cache takes back (mr_devmem.hpp: it keeps up to 16 GiB):
+// a matrix plan's rows must fit one.
+static constexpr uint64_t kMatrixMaxBytes = uint64_t(16) << 30;
+
+// matrix plans: the destinations resolved once into 8 B each (KArgs::mx_dst) and the record
+// rows, [plan source][pitch], pitch = n_dst rounded up to whole 128 B lines
+static int plan_matrix_outputs(mr_plan *pl) {
+    const HostPlan &hp = pl->hp;
+    KArgs &ka = pl->ka;
+    mr_plan::Matrix &m = pl->mx;
+    const mr_grid *g = pl->grid;
+    m.n_dst = uint32_t(m.dst_v.size());
+    const uint64_t pitch = (uint64_t(m.n_dst) + 7) / 8 * 8, ns = std::max<uint32_t>(ka.nsrc, 1);
+    if (pitch > 0xFFFFFFFFull || ns * pitch > kMatrixMaxBytes / sizeof(mr_label_record))
+        return fail(MR_ERR_LIMIT, "matrix plan: " + std::to_string(ns) + " sources x " + std::to_string(pitch) +
+                                      " records of 16 B exceed the device block cache's largest block");
+    m.pitch = uint32_t(pitch);
+    std::vector<std::pair<uint32_t, uint32_t>> spv;  // (cell, table index) of the specials
+    for (uint32_t t = 1; t <= hp.p.NS; ++t) spv.push_back({hp.sp[t].v, t});
+    std::sort(spv.begin(), spv.end());
+    std::vector<uint2> d(m.n_dst);
+    for (uint32_t j = 0; j < m.n_dst; ++j) {
+        const uint32_t v = m.dst_v[j];
+        const auto it = std::lower_bound(spv.begin(), spv.end(), std::make_pair(v, 0u));
+        d[j].x = (uint32_t(g->gx(v)) & 0xFFFFu) | (uint32_t(g->gy(v)) << 16);
+        d[j].y = it != spv.end() && it->first == v ? (kViaSpecial | it->second) : (v & ~kViaSpecial);
+    }
+    if (upload(m.dst, d) != hipSuccess || m.rows.alloc(size_t(ns * pitch)) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "hipMalloc matrix outputs");
+    ka.mx_dst = m.dst.get();
+    ka.mx_rows = m.rows.get();
+    ka.mx_ndst = m.n_dst;
+    ka.mx_pitch = m.pitch;
+    m.per_cu = uint32_t(std::max(1, matrix_blocks_per_cu(hp.p.perm)));
     return MR_OK;
 }
 
@@ -2695,7 +2746,8 @@ static void plan_diag(mr_plan *pl) {
 // pass is shorter than a fill, and 3 or 4 slots measured the same pass time)
 static int plan_overlap(mr_plan *pl) {
     const HostPlan &hp = pl->hp;
-    if (!pl->all_mode || !hp.hub || env_is("MR_FILL_OVERLAP", "0")) return MR_OK;
+    // (matrix plans: serial launches on the pass's stream, one slot)
+    if (!pl->all_mode || pl->matrix || !hp.hub || env_is("MR_FILL_OVERLAP", "0")) return MR_OK;
     uint32_t nslots = 2;
     if (const char *e = std::getenv("MR_FILL_SLOTS")) nslots = uint32_t(std::min(8, std::max(2, std::atoi(e))));
     const size_t T = size_t(hp.p.NS) + 1, ns = std::max<size_t>(pl->ka.nsrc, 1);
@@ -2722,7 +2774,7 @@ static int plan_overlap(mr_plan *pl) {
 }
 
 static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *qs, uint32_t n, uint32_t max_cmds,
-                       mr_plan **out, bool all_mode = false) {
+                       mr_plan **out, bool all_mode = false, std::vector<uint32_t> *matrix_dst = nullptr) {
     if (!out || (n && !qs)) return fail(MR_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     if (!mr_device_available()) return fail(MR_ERR_NO_DEVICE, "no gfx950 device visible (no CPU fallback)");
@@ -2733,6 +2785,8 @@ static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *q
     std::unique_ptr<mr_plan> pl(new mr_plan());
     pl->grid = g;
     pl->all_mode = all_mode;
+    pl->matrix = matrix_dst != nullptr;
+    if (matrix_dst) pl->mx.dst_v = std::move(*matrix_dst);
     HostPlan &hp = pl->hp;
     int st = build_plan(g, prm, qs, n, max_cmds, hp, !all_mode);
     if (st == MR_OK && hp.dev_grouped) {  // the batch grouped on the device (counts back)
@@ -2753,6 +2807,7 @@ static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *q
     if (pl->stream.create() != hipSuccess) return fail(MR_ERR_DEVICE, "stream");
     plan_base_args(pl.get(), n);
     if (all_mode && (st = plan_all_outputs(pl.get(), n))) return st;
+    if (pl->matrix && (st = plan_matrix_outputs(pl.get()))) return st;
     if (hp.hub && ((st = plan_hub(pl.get())) || (st = plan_cert(pl.get())) || (st = plan_lane(pl.get())))) return st;
     if ((st = plan_lane_memo(pl.get()))) return st;
     plan_diag(pl.get());
@@ -2851,6 +2906,11 @@ static hipError_t run_all(mr_plan *pl, hipStream_t s) {
     const mr_plan::Slot &k = pl->cur();
     uint32_t gx = resident_grid((fill_items(pl) + 3) / 4, uint64_t(pl->hub.fill_per_cu) * pl->cus);
     if (const char *e = std::getenv("MR_FILL_GX")) gx = uint32_t(std::max(1, std::atoi(e)));
+    if (pl->matrix) {  // (source, 64-destination chunk) items, one per wave; MR_MATRIX_GX fixes the grid
+        const uint64_t items = uint64_t(pl->ka.nsrc) * ((pl->mx.pitch + 63) / 64);
+        gx = resident_grid((items + 3) / 4, uint64_t(pl->mx.per_cu) * pl->cus);
+        if (const char *e = std::getenv("MR_MATRIX_GX")) gx = uint32_t(std::max(1, std::atoi(e)));
+    }
     const hipStream_t hs = pl->overlap ? pl->hub_stream.get() : s;
     hipError_t e = launch_hub_plan(pl, k.args.get(), hs);
     if (e == hipSuccess && pl->overlap &&
@@ -2859,7 +2919,9 @@ static hipError_t run_all(mr_plan *pl, hipStream_t s) {
     if (e == hipSuccess && !pl->fb_none) e = launch_fallback(pl, k, s);
     Event f0;
     if (e == hipSuccess) f0 = fill_start(s);
-    if (e == hipSuccess) e = launch_fill(k.args_fill.get(), pl->ka.p.perm, gx, 1, s);
+    if (e == hipSuccess)
+        e = pl->matrix ? launch_matrix(k.args_fill.get(), pl->ka.p.perm, gx, s)
+                       : launch_fill(k.args_fill.get(), pl->ka.p.perm, gx, 1, s);
     // the slot's tables are free again once this fill has read them
     if (e == hipSuccess && pl->overlap && hipEventRecord(k.ev_fill.get(), s) != hipSuccess) e = hipErrorUnknown;
     pl->timed_fill.push_back({std::move(f0), nullptr, false});  // one per pass (f0 may be empty), as in `timed`
@@ -3032,8 +3094,10 @@ extern "C" double mr_plan_kernel_ms(mr_plan *pl, uint32_t *n_launches) {
     // all-destinations passes: the fill launches' own time (their end event is the pass's)
     fold_timed(pl, 0);
     pl->fill_ms = pl->acc_fill_n ? pl->acc_fill_ms / pl->acc_fill_n : 0.0;
-    const double tot = pl->acc_ms;
-    const uint32_t k = pl->acc_n;
+    // (a matrix plan's main kernel is its read-off: the matrix launches of the hub passes)
+    const bool mx = pl->matrix && pl->acc_fill_n;
+    const double tot = mx ? pl->acc_fill_ms : pl->acc_ms;
+    const uint32_t k = mx ? pl->acc_fill_n : pl->acc_n;
     pl->acc_ms = pl->acc_fill_ms = 0.0;
     pl->acc_n = pl->acc_fill_n = 0;
     uint32_t ctr[kCtrWords];
@@ -3218,6 +3282,7 @@ extern "C" int mr_plan_wait(mr_plan *pl, void *stream) {
 
 extern "C" int mr_plan_device_outputs(mr_plan *pl, void **d_results, uint64_t *rb, void **d_commands, uint64_t *cb) {
     if (!pl) return fail(MR_ERR_INVALID_ARG, "null plan");
+    if (pl->matrix) return fail(MR_ERR_INVALID_ARG, "device_outputs: not a query plan (mr_matrix_device_records)");
     // the pointers are handed out once the plan's passes so far have finished, so a
     // raw read right after this call sees whole records (mr_plan_wait orders a stream
     // instead of the host)
@@ -3522,6 +3587,7 @@ static bool plan_fetch_wire(mr_plan *pl, mr_result *results, mr_command *pool, u
 
 extern "C" int mr_plan_fetch(mr_plan *pl, mr_result *results, mr_command *pool, uint64_t pool_cap) {
     if (!pl || (pl->hp.nq && !results)) return fail(MR_ERR_INVALID_ARG, "null argument");
+    if (pl->matrix) return fail(MR_ERR_INVALID_ARG, "fetch: not a query plan (mr_matrix_records)");
     {
         int ret = MR_OK;
         if (plan_fetch_wire(pl, results, pool, pool_cap, ret)) return ret;
@@ -3981,7 +4047,7 @@ extern "C" int mr_sssp_plan_create(const mr_grid *g, const mr_params *prm, const
 }
 
 static int sssp_source(mr_plan *pl, uint32_t i, uint32_t &si) {
-    if (!pl || !pl->all_mode) return fail(MR_ERR_INVALID_ARG, "not an all-destinations plan");
+    if (!pl || !pl->all_mode || pl->matrix) return fail(MR_ERR_INVALID_ARG, "not an all-destinations plan");
     if (i >= pl->src_of_input.size() || pl->src_of_input[i] == kNone32) return fail(MR_ERR_INVALID_ARG, "source index");
     si = pl->src_of_input[i];
     uint32_t flags = 0;
@@ -4000,23 +4066,9 @@ static int sssp_table(mr_plan *pl, uint32_t si, std::vector<Rec> &tab) {
 // A cell word (CellWord, mr_engine.hpp) over its source's table: the label's metrics
 // (the table label's plus the final walk's) and `via`.  False if it names no entry.
 static bool expand_word(const HostPlan &hp, const std::vector<Rec> &tab, CellWord w, mr_label_record &o) {
-    const uint32_t T = uint32_t(tab.size());
-    if (w == kViaSource) {
-        o = mr_label_record{0, 0, 0, kViaSource};
-        return true;
-    }
-    if (w & kViaSpecial) {
-        const uint32_t t = w & kNone10;
-        if (t >= T || (w & ~(kViaSpecial | kNone10))) return false;
-        o = mr_label_record{tab[t].m[0], tab[t].m[1], tab[t].m[2], w};
-        return true;
-    }
-    const uint32_t b = w >> kStBShift, k = w & kStKMask;
-    if (b >= T) return false;
-    // AggregatedCost::time of the walk's run (src/cost.rs:122-124): Fleetfoot's ceil
-    const uint64_t t = (uint64_t(180) * k * hp.p.ff_num + hp.p.ff_den - 1) / hp.p.ff_den;
-    o = mr_label_record{tab[b].m[0] + k, tab[b].m[1], uint32_t(tab[b].m[2] + t), b};
-    return true;
+    // (the rule itself: mr_label.hpp, shared with the kernels that write matrix records)
+    return mr::expand_word(w, uint32_t(tab.size()), FfRatio{hp.p.ff_num, hp.p.ff_den},
+                           [&](uint32_t t, uint32_t q) { return tab[t].m[q]; }, o);
 }
 
 // A source's cell words in row-major order (S x S, the device rows' padding dropped):
@@ -4050,7 +4102,7 @@ extern "C" int mr_sssp_records(mr_plan *pl, uint32_t i, mr_label_record *out) {
 }
 
 extern "C" int mr_sssp_device_records(mr_plan *pl, void **d_records, uint64_t *bytes) {
-    if (!pl || !pl->all_mode) return fail(MR_ERR_INVALID_ARG, "not an all-destinations plan");
+    if (!pl || !pl->all_mode || pl->matrix) return fail(MR_ERR_INVALID_ARG, "not an all-destinations plan");
     if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // whole records behind the pointer
     if (d_records) *d_records = pl->out.rec.get();
     if (bytes) *bytes = uint64_t(pl->ka.nsrc) * pl->ka.p.S * pl->ka.rec_pitch * sizeof(CellWord);
@@ -4058,14 +4110,14 @@ extern "C" int mr_sssp_device_records(mr_plan *pl, void **d_records, uint64_t *b
 }
 
 extern "C" int mr_sssp_record_pitch(mr_plan *pl, uint32_t *cells_per_row) {
-    if (!pl || !pl->all_mode) return fail(MR_ERR_INVALID_ARG, "not an all-destinations plan");
+    if (!pl || !pl->all_mode || pl->matrix) return fail(MR_ERR_INVALID_ARG, "not an all-destinations plan");
     if (!cells_per_row) return fail(MR_ERR_INVALID_ARG, "null output");
     *cells_per_row = pl->ka.rec_pitch;
     return MR_OK;
 }
 
 extern "C" int mr_sssp_device_tables(mr_plan *pl, void **d_tables, uint64_t *bytes) {
-    if (!pl || !pl->all_mode) return fail(MR_ERR_INVALID_ARG, "not an all-destinations plan");
+    if (!pl || !pl->all_mode || pl->matrix) return fail(MR_ERR_INVALID_ARG, "not an all-destinations plan");
     if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // the latest pass's slot, finished
     if (d_tables) *d_tables = pl->cur().tab.get();
     if (bytes) *bytes = uint64_t(pl->ka.nsrc) * (pl->ka.p.NS + 1) * sizeof(Rec);
@@ -4185,4 +4237,115 @@ extern "C" int mr_sssp_labels(mr_plan *pl, uint32_t i, mr_result *results, mr_co
         off += seq.size();
     }
     return ret;
+}
+
+// ------------------------------------------------------------ cost matrices
+extern "C" int mr_matrix_plan_create(const mr_grid *g, const mr_params *prm, const mr_cell_index *sources, uint32_t n_src,
+                                     const mr_cell_index *dests, uint32_t n_dst, mr_plan **out) {
+    if (!g || !prm || !out || !sources || !dests) return fail(MR_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!n_src || !n_dst) return fail(MR_ERR_INVALID_ARG, "a matrix plan needs at least one source and one destination");
+    if (!mr_device_available()) return fail(MR_ERR_NO_DEVICE, "no gfx950 device visible (no CPU fallback)");
+    std::vector<uint32_t> dv(n_dst);
+    for (uint32_t i = 0; i < n_src; ++i) {
+        uint32_t v;
+        if (!g->find(sources[i], v)) return fail(MR_ERR_INVALID_INDEX, "source " + std::to_string(i) + " is not a grid cell");
+    }
+    for (uint32_t j = 0; j < n_dst; ++j)
+        if (!g->find(dests[j], dv[j]))
+            return fail(MR_ERR_INVALID_INDEX, "destination " + std::to_string(j) + " is not a grid cell");
+    std::vector<mr_query> qs(n_src);
+    for (uint32_t i = 0; i < n_src; ++i) qs[i].from = qs[i].to = sources[i];
+    const int st = plan_create(g, prm, qs.data(), n_src, 16, out, true, &dv);
+    if (st == MR_OK) (*out)->mx.n_src = n_src;
+    return st;
+}
+
+// a matrix plan whose last pass raised no device error (waits for the plan)
+static int matrix_plan(mr_plan *pl) {
+    if (!pl || !pl->matrix) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    uint32_t flags = 0;
+    return check_device_errors(pl, flags);
+}
+
+extern "C" int mr_matrix_records(mr_plan *pl, mr_label_record *out, uint64_t cap_records) {
+    if (int st = matrix_plan(pl)) return st;
+    if (!out) return fail(MR_ERR_INVALID_ARG, "null output");
+    const mr_plan::Matrix &m = pl->mx;
+    if (cap_records < uint64_t(m.n_src) * m.n_dst) return fail(MR_ERR_CAPACITY, "mr_matrix_records: output shorter than n_src x n_dst");
+    // No host copy of the padded rows (1 GB at 1 024 x 65 536).  Rows without padding whose
+    // order is the caller's: one copy.  Else each caller source's row on its own, a contiguous
+    // run of n_dst records (plain copies: see copy_source_words on pitched ones).
+    const mr_label_record *rows = reinterpret_cast<const mr_label_record *>(m.rows.get());
+    bool in_order = m.pitch == m.n_dst;
+    for (uint32_t i = 0; i < m.n_src && in_order; ++i) in_order = pl->src_of_input[i] == i;
+    hipError_t e = hipSuccess;
+    if (in_order) {
+        e = hipMemcpy(out, rows, size_t(m.n_src) * m.n_dst * sizeof(mr_label_record), hipMemcpyDeviceToHost);
+    } else {
+        for (uint32_t i = 0; i < m.n_src && e == hipSuccess; ++i)
+            e = hipMemcpy(out + size_t(i) * m.n_dst, rows + size_t(pl->src_of_input[i]) * m.pitch,
+                          size_t(m.n_dst) * sizeof(mr_label_record), hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) return fail(MR_ERR_DEVICE, std::string("copy matrix records: ") + hipGetErrorString(e));
+    return MR_OK;
+}
+
+extern "C" int mr_matrix_device_records(mr_plan *pl, void **d_records, uint64_t *bytes) {
+    if (!pl || !pl->matrix) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // whole records behind the pointer
+    if (d_records) *d_records = pl->mx.rows.get();
+    if (bytes) *bytes = uint64_t(pl->ka.nsrc) * pl->mx.pitch * sizeof(mr_label_record);
+    return MR_OK;
+}
+
+extern "C" int mr_matrix_record_pitch(mr_plan *pl, uint32_t *records_per_row) {
+    if (!pl || !pl->matrix) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!records_per_row) return fail(MR_ERR_INVALID_ARG, "null output");
+    *records_per_row = pl->mx.pitch;
+    return MR_OK;
+}
+
+extern "C" int mr_matrix_source_rows(const mr_plan *pl, uint32_t *row_of_source, uint32_t n_src) {
+    if (!pl || !pl->matrix) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (n_src && !row_of_source) return fail(MR_ERR_INVALID_ARG, "null output");
+    for (uint32_t i = 0; i < n_src; ++i) row_of_source[i] = i < pl->src_of_input.size() ? pl->src_of_input[i] : kNone32;
+    return MR_OK;
+}
+
+extern "C" int mr_matrix_label(mr_plan *pl, uint32_t i, uint32_t j, mr_result *res, mr_command *cmds, uint32_t cap) {
+    if (int st = matrix_plan(pl)) return st;
+    if (!res) return fail(MR_ERR_INVALID_ARG, "null result");
+    const mr_plan::Matrix &m = pl->mx;
+    if (i >= m.n_src || j >= m.n_dst) return fail(MR_ERR_INVALID_ARG, "matrix index");
+    const uint32_t si = pl->src_of_input[i], w = m.dst_v[j];
+    mr_label_record got;
+    std::vector<Rec> tab;
+    if (hipMemcpy(&got, m.rows.get() + size_t(si) * m.pitch + j, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "copy label");
+    if (int st = sssp_table(pl, si, tab)) return st;
+    // the cell word the record expands: a walk's length is its legs over the boundary's
+    CellWord word = got.via;
+    if (got.via != kViaSource && !(got.via & kViaSpecial)) {
+        if (got.via >= tab.size() || got.legs - tab[got.via].m[0] > kStKMask)
+            return fail(MR_ERR_DEVICE, "record names no boundary");
+        word = (got.via << kStBShift) | (got.legs - tab[got.via].m[0]);
+    }
+    mr_label_record rec;
+    std::vector<OutCmd> seq;
+    if (int st = sssp_expand(pl, si, tab, w, word, rec, seq)) return st;
+    if (std::memcmp(&rec, &got, sizeof(rec)) != 0) return fail(MR_ERR_DEVICE, "record is not its cell word's expansion");
+    std::memset(res, 0, sizeof(*res));
+    res->legs = rec.legs;
+    res->money = rec.money;
+    res->time_s = int64_t(rec.time_s);
+    res->n_commands = uint32_t(seq.size());
+    if (seq.size() > cap || (!cmds && !seq.empty())) {
+        res->status = MR_ERR_CAPACITY;
+        return MR_ERR_CAPACITY;
+    }
+    const CmdScale cs = cmd_scale(pl->hp);
+    for (size_t q = 0; q < seq.size(); ++q)
+        if (!expand_cmd(pl->grid, cs, seq[q], cmds[q])) return fail(MR_ERR_DEVICE, "command names no cell");
+    return MR_OK;
 }

@@ -97,6 +97,30 @@ __host__ __device__ inline uint64_t label_time_add(const CmdCost &c, const FfRat
     return c.kind == kStandard ? (t * r.num + r.den - 1) / r.den : t;
 }
 
+// ---- cell words (mr_engine.hpp CellWord) ----
+// A cell word over its source's label table of T entries: the label's metrics (the table
+// label's plus the final walk's: k legs, no money, the run's Fleetfoot ceil, src/cost.rs:122-124)
+// and `via`.  metric(t, q) = metric q of table entry t.  False if the word names no entry.
+// One rule for mr_sssp_records on the host, the matrix kernel and the SSSP kernel's matrix rows.
+template <class Metric>
+__host__ __device__ inline bool expand_word(CellWord w, uint32_t T, const FfRatio &ff, Metric metric, mr_label_record &o) {
+    if (w == kViaSource) {
+        o = mr_label_record{0u, 0u, 0u, kViaSource};
+        return true;
+    }
+    if (w & kViaSpecial) {
+        const uint32_t t = w & kNone10;
+        if (t >= T || (w & ~(kViaSpecial | kNone10))) return false;
+        o = mr_label_record{metric(t, 0u), metric(t, 1u), metric(t, 2u), w};
+        return true;
+    }
+    const uint32_t b = w >> kStBShift, k = w & kStKMask;
+    if (b >= T) return false;
+    const uint32_t run = ff.num == ff.den ? 180u * k : uint32_t((uint64_t(180) * k * ff.num + ff.den - 1) / ff.den);
+    o = mr_label_record{metric(b, 0u) + k, metric(b, 1u), metric(b, 2u) + run, b};
+    return true;
+}
+
 // ---- wire rows (mr_engine.hpp: Wire records) ----
 // The header of wire row `row` (max_cmds mc; wp: the wire pool of pool_n commands).  A
 // label: nc commands of two words each at src, the first one's `from` rank in `from`.  A

@@ -30,6 +30,8 @@ EXPORTED_SYMBOLS = [
     "mr_device_available", "mr_parse_map_html", "mr_parse_error", "mr_grid_from_html",
     "mr_command_time", "mr_duration_display", "mr_render_schedule", "mr_grid_region_table",
     "mr_sssp_plan_create", "mr_sssp_records", "mr_sssp_device_records", "mr_sssp_record_pitch", "mr_sssp_device_tables", "mr_sssp_label", "mr_sssp_labels", "mr_plan_fill_ms",
+    "mr_matrix_plan_create", "mr_matrix_records", "mr_matrix_device_records", "mr_matrix_record_pitch",
+    "mr_matrix_source_rows", "mr_matrix_label",
 ]
 
 
@@ -148,6 +150,20 @@ def lib():
         L.mr_grid_region_table.restype = C.c_int
         L.mr_plan_fill_ms.argtypes = [vp]
         L.mr_plan_fill_ms.restype = C.c_double
+        L.mr_matrix_plan_create.argtypes = [vp, C.POINTER(mr_params), C.POINTER(mr_cell_index), C.c_uint32,
+                                            C.POINTER(mr_cell_index), C.c_uint32, C.POINTER(vp)]
+        L.mr_matrix_plan_create.restype = C.c_int
+        L.mr_matrix_records.argtypes = [vp, vp, C.c_uint64]
+        L.mr_matrix_records.restype = C.c_int
+        L.mr_matrix_device_records.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.mr_matrix_device_records.restype = C.c_int
+        L.mr_matrix_record_pitch.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.mr_matrix_record_pitch.restype = C.c_int
+        L.mr_matrix_source_rows.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint32]
+        L.mr_matrix_source_rows.restype = C.c_int
+        L.mr_matrix_label.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(mr_result), C.POINTER(mr_command),
+                                      C.c_uint32]
+        L.mr_matrix_label.restype = C.c_int
         _lib = L
     return _lib
 
@@ -302,6 +318,13 @@ class FindPath:
             raise EngineError(st, last_error())
         res.command_offset = 0
         return result_from_c(res, cmds)
+
+    def eval_matrix(self, sources: Sequence[CellIndex], dests: Sequence[CellIndex]):
+        """The metrics of every (source, destination) label after one pass of a MatrixPlan:
+        a (n_src, n_dst, 4) uint32 array of legs, money, time, via."""
+        plan = MatrixPlan(self.grid, self.params(), sources, dests)
+        plan.run()
+        return plan.records()
 
     def eval_batch_raw(self, pairs: Sequence[Tuple[CellIndex, CellIndex]]):
         n = len(pairs)
@@ -682,3 +705,80 @@ class SSSPPlan(Plan):
 
     def fetch(self):
         raise NotImplementedError("all-destinations plans: use records() / label()")
+
+
+def _cell_array(cells: Sequence[CellIndex]):
+    arr = (mr_cell_index * max(len(cells), 1))()
+    for i, c in enumerate(cells):
+        arr[i].kind, arr[i].sub, arr[i].x, arr[i].y = c.kind, c.sub, c.x, c.y
+    return arr
+
+
+class MatrixPlan(Plan):
+    """Cost matrix: run() computes one 16 B record (legs, money, time, via) for every
+    (source, listed destination) pair on the device; label(i, j) rebuilds the full TotalCost."""
+
+    def __init__(self, grid: MapGrid, params: Params, sources: Sequence[CellIndex], dests: Sequence[CellIndex]):
+        self.grid = grid
+        self.n = len(sources)
+        self.n_dst = len(dests)
+        self.sources = list(sources)
+        self.dests = list(dests)
+        self._p = params.to_c()
+        h = C.c_void_p()
+        st = lib().mr_matrix_plan_create(grid.handle, C.byref(self._p), _cell_array(sources), self.n,
+                                         _cell_array(dests), self.n_dst, C.byref(h))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        self.handle = h
+
+    def records(self):
+        """(n_src, n_dst, 4) uint32 array: legs, money, time, via of source i x destination j."""
+        import numpy as np
+        out = np.empty((self.n, self.n_dst, 4), dtype=np.uint32)
+        st = lib().mr_matrix_records(self.handle, out.ctypes.data, self.n * self.n_dst)
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return out
+
+    def device_records(self):
+        """(device pointer, bytes) of the rows: [plan source][record_pitch()] records of 16 B."""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        st = lib().mr_matrix_device_records(self.handle, C.byref(ptr), C.byref(n))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return ptr.value, n.value
+
+    def record_pitch(self) -> int:
+        """Records per row of device_records() (n_dst rounded up to a multiple of 8)."""
+        p = C.c_uint32()
+        st = lib().mr_matrix_record_pitch(self.handle, C.byref(p))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return p.value
+
+    def source_rows(self) -> List[int]:
+        """The device row of each of the caller's sources (repeated sources share a row)."""
+        out = (C.c_uint32 * max(1, self.n))()
+        st = lib().mr_matrix_source_rows(self.handle, out, self.n)
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return list(out)[:self.n]
+
+    def label(self, i: int, j: int) -> TotalCost:
+        res = mr_result()
+        cap = 64
+        while True:
+            cmds = (mr_command * cap)()
+            st = lib().mr_matrix_label(self.handle, i, j, C.byref(res), cmds, cap)
+            if st == MR_ERR_CAPACITY and res.n_commands > cap:
+                cap = res.n_commands
+                continue
+            break
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        res.command_offset = 0
+        return result_from_c(res, cmds)
+
+    def fetch(self):
+        raise NotImplementedError("matrix plans: use records() / label()")
