@@ -1,6 +1,6 @@
 """Maps the synthetic generator never draws, in every orientation (test infrastructure for
-test_irregular_maps.py on the CPU and test_gpu_irregular_maps.py on the device; no engine
-import).
+test_irregular_maps.py on the CPU, test_gpu_irregular_maps.py and
+test_gpu_oriented_all_destinations.py on the device; no engine import).
 
 SyntheticMap(size, campfires_per_homeland=k) gives every homeland the same number of
 campfires, campfires on homeland cells only, and the one standard orientation.  A map
@@ -236,6 +236,96 @@ def py_ref_labels(name, k, pi, n=150):
     if key not in _labels:
         _labels[key] = finder_labels(finder_for(name, k, pi), capped_queries(name, n))
     return _labels[key]
+
+
+def sssp_sources(m):
+    """The sources of the all-destinations and matrix tests: the Center, a border campfire (a
+    border-1 cell where the map has none), a homeland campfire and a plain cell."""
+    cells = m.all_indices()
+    off = off_homeland_campfires(m)
+    home = [c for c in m.campfires() if c not in off]
+    plain = [c for c in cells if c not in specials(m)]
+    out = [CellIndex.center(), off[-1] if off else CellIndex.border(1, 1), home[0]]
+    return out + ([plain[len(plain) // 2]] if plain else [CellIndex.border(3, 1)])
+
+
+def matrix_sources(m):
+    """sssp_sources(m) and its last source once more: matrix plans keep one row for both."""
+    s = sssp_sources(m)
+    return s + [s[3]]
+
+
+# How many of sssp_sources(m) the transposed all-destinations tests give py_ref, the Center
+# and the plain cell first: one (map, layout, parameter set) must stay under about 5 s of
+# py_ref (the measured seconds: test_gpu_oriented_all_destinations.py's docstring).
+TRANSPOSED_SOURCE_ORDER = (0, 3, 2, 1)
+TRANSPOSED_SOURCES = {"unequal9": 4, "unequal": 3, "wide15": 2}
+
+
+def transposed_sources(name):
+    s = sssp_sources(get_map(name))
+    return [s[i] for i in TRANSPOSED_SOURCE_ORDER[:TRANSPOSED_SOURCES[name]]]
+
+
+_all = {}
+
+
+def py_ref_all(name, k, pi, sources):
+    """py_ref's labels of every cell of orientation k (in its cells() order) from each of
+    sources under params_for(..)[pi], [source][cell] in golden_util.as_expected's form; computed
+    once per (map, orientation, params, source)."""
+    cells = oriented(name, k).all_indices()
+    out = []
+    for s in sources:
+        key = (name, k, pi, s)
+        if key not in _all:
+            _all[key] = finder_labels(finder_for(name, k, pi), [(s, d) for d in cells])
+        out.append(_all[key])
+    return out
+
+
+def tie_cells(m, params, source, labels):
+    """The plain cells of m (a map or an Oriented) whose label from `source` is decided by a
+    tie: another boundary (the source or a special but the Center) reaches the cell by a walk
+    with the same legs, money and time as the label and other commands.  `labels` are the
+    reference's labels of m.all_indices() from `source` in as_expected's form; params must have
+    Fleetfoot 0, so that a walk of k cells adds k legs and 180 k seconds to its boundary's
+    label, whether or not it lengthens that label's last walk."""
+    assert params.fleetfoot == 0
+    STANDARD, NOMOVE = 2, 0
+    S, H = m.size, m.size // 2
+    cells = m.all_indices()
+    pos = {c: (j % S - H, j // S - H) for j, c in enumerate(cells)}
+    at = {c: j for j, c in enumerate(cells)}
+    sp = [c for c in dict.fromkeys([source] + specials(m) + ([params.hq_position] if params.hq_position else []))
+          if c != CellIndex.center()]
+    out = []
+    for d, lab in zip(cells, labels):
+        if d in sp or d == CellIndex.center() or lab is None:
+            continue
+        to = [d.kind, d.sub, d.x, d.y]
+        for b in sp:
+            base = labels[at[b]]
+            if base is None:
+                continue
+            (ax, ay), (bx, by) = pos[b], pos[d]
+            k = abs(ax - bx) + abs(ay - by)
+            if (ay == 0 and by == 0 and (ax < 0) != (bx < 0)) or (ax == 0 and bx == 0 and (ay < 0) != (by < 0)):
+                k += 2  # the walk goes round the Center
+            if [base[0] + k, base[1], base[2] + 180 * k] != lab[:3]:
+                continue
+            cmds = [list(c) for c in base[3]]
+            last = cmds[-1]
+            if last[0] == STANDARD:
+                cmds[-1] = [STANDARD, last[1] + 180 * k, last[2] + k, 0, 0, last[5], to]
+            elif last[0] == NOMOVE:
+                cmds[-1] = [STANDARD, 180 * k, k, 0, 0, last[5], to]
+            else:
+                cmds.append([STANDARD, 180 * k, k, 0, 0, [b.kind, b.sub, b.x, b.y], to])
+            if cmds != lab[3]:
+                out.append(d)
+                break
+    return out
 
 
 def py_ref_some(name_or_map, k, params, qs):

@@ -20,7 +20,7 @@ import pytest
 
 import irregular_maps as im
 from golden_util import as_expected
-from marshrutka_amd.abi import BLUE, CellIndex, Params, result_from_c
+from marshrutka_amd.abi import BLUE, Params, result_from_c
 from marshrutka_amd.mapgen import SyntheticMap, random_query_cells
 from test_gpu_decode_widths import DeviceWords, hip  # noqa: F401  (hip: a fixture)
 from test_gpu_dev_group import _run, _same
@@ -163,15 +163,6 @@ def test_homeland_changes_the_table_shape(eng, monkeypatch):  # noqa: F811
     assert shapes == [(9, 18), (1, 18), (2, 18), (1, 18)], shapes
 
 
-def _sssp_sources(m):
-    cells = m.all_indices()
-    off = im.off_homeland_campfires(m)
-    home = [c for c in m.campfires() if c not in off]
-    plain = [c for c in cells if c not in im.specials(m)]
-    out = [CellIndex.center(), off[-1] if off else CellIndex.border(1, 1), home[0]]
-    return out + ([plain[len(plain) // 2]] if plain else [CellIndex.border(3, 1)])
-
-
 @pytest.mark.parametrize("name", ["unequal", "border1", "ties", "s3"])
 def test_all_destinations(eng, oracle_lib, mode, name):  # noqa: F811
     """An all-destinations plan from the Center, a border campfire (a border-1 cell where the
@@ -179,7 +170,7 @@ def test_all_destinations(eng, oracle_lib, mode, name):  # noqa: F811
     m = im.get_map(name)
     prm = im.params_for(m)
     for params in (prm[0], prm[1], prm[2]) if m.size > 3 else prm:
-        all_labels_match(eng, oracle_lib, m, params, _sssp_sources(m))
+        all_labels_match(eng, oracle_lib, m, params, im.sssp_sources(m))
 
 
 @pytest.mark.parametrize("name", ["unequal", "ties", "corners", "s3", "s5_full"])

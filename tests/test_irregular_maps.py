@@ -52,6 +52,60 @@ def test_oracle_differs_from_py_ref_on_transposed_9(oracle_lib, k):
     assert pairs >= 1 and diff >= 1
 
 
+def _oracle_all(oracle_lib, name, k, pi, sources):
+    """The oracle's labels of every cell of orientation k from each source, [source][cell]."""
+    om = im.oriented(name, k)
+    return [_oracle_labels(oracle_lib, name, k, pi, [(s, d) for d in om.all_indices()]) for s in sources]
+
+
+@pytest.mark.parametrize("k", im.TRANSPOSED)
+def test_transposed_all_destinations_tell_py_ref_from_the_oracle(oracle_lib, k):
+    """A premise of test_gpu_oriented_all_destinations.py's transposed tests: from the sources
+    they use, under parameter set 0 (Blue, nine regions), some cell's py_ref label is not the
+    oracle's, so an engine that followed the reference's projection shortcut would fail them."""
+    sources = im.transposed_sources("unequal9")
+    ref = im.py_ref_all("unequal9", k, 0, sources)
+    diff = [sum(a != b for a, b in zip(o, r)) for o, r in zip(_oracle_all(oracle_lib, "unequal9", k, 0, sources), ref)]
+    print(f"unequal9 k={k} params 0: labels that differ, by source: {diff} of 81 each")
+    assert sum(diff) >= 1, diff
+
+
+@pytest.mark.parametrize("name", im.ORIENTED)
+def test_all_destinations_sources_meet_ties(oracle_lib, name):
+    """The other premise: on every map of the mirrored and the transposed tests, the chosen
+    sources reach some plain cell by two boundaries with equal legs, money and time and
+    different commands (irregular_maps.tie_cells, parameter set 0), so the boundaries' order,
+    which the kernels take from the layout's rank table, decides a label the tests compare.
+    Mirrored layouts from the oracle's labels; transposed ones from py_ref's, every layout of
+    the 9 x 9 map and one of each 15 x 15 map (py_ref takes a second a source there)."""
+    m = im.get_map(name)
+    params = im.params_for(m)[0]
+    for k in im.MIRRORED:
+        sources = im.sssp_sources(m)
+        labels = _oracle_all(oracle_lib, name, k, 0, sources)
+        n = [len(im.tie_cells(im.oriented(name, k), params, s, lab)) for s, lab in zip(sources, labels)]
+        assert sum(n) >= 1, f"{name} k={k}: {sum(n)} tie cells, by source {n}"
+    for k in im.TRANSPOSED if m.size == 9 else (5,):
+        sources = im.transposed_sources(name)
+        labels = im.py_ref_all(name, k, 0, sources)
+        n = [len(im.tie_cells(im.oriented(name, k), params, s, lab)) for s, lab in zip(sources, labels)]
+        print(f"{name} k={k}: {sum(n)} tie cells, by source {n}")
+        assert sum(n) >= 1, f"{name} k={k}: {sum(n)} tie cells, by source {n}"
+
+
+def test_tie_cells_on_a_case_worked_by_hand():
+    """tie_cells itself.  From the Center with scrolls and caravans off, a label is one
+    CentralMove to a border-1 cell and a walk.  A homeland cell is as far from the border-1
+    cell on either of its two axes (a tie); a border cell is nearer the one on its own axis."""
+    from marshrutka_amd.abi import CellIndex, Params
+    m = im.get_map("unequal9")
+    params = Params(use_soe=False, use_caravans=False)
+    f = im.py_ref.Finder(im.finder_for("unequal9", 0, 0).g, params.to_json())
+    labels = im.finder_labels(f, [(CellIndex.center(), d) for d in m.all_indices()])
+    want = [c for c in m.all_indices() if c.kind == CELL_HOMELAND and c not in im.specials(m)]
+    assert want and im.tie_cells(m, params, CellIndex.center(), labels) == want
+
+
 @pytest.mark.parametrize("name", im.CATALOGUE + ["unequal9", "wide15", "unequal21"])
 def test_projection_equals_direct_argmin_on_the_given_orientation(oracle_lib, name):
     m = im.get_map(name)
