@@ -475,6 +475,55 @@ int mr_matrix_source_rows(const mr_plan *plan, uint32_t *row_of_source, uint32_t
  * MR_OK, MR_ERR_CAPACITY (out->n_commands > cap) or an error */
 int mr_matrix_label(mr_plan *plan, uint32_t i, uint32_t j, mr_result *out, mr_command *cmds, uint32_t cap);
 
+/* ---- nearest of a set: the best listed destination per source and group -- */
+/* A matrix plan reduced on the device.  group_of_dst[j] < n_groups names the group of
+ * destination j (NULL: all in group 0).  For caller source i and group g the winner is the
+ * destination j of the group with the least (m[q0], m[q1], m[q2], j): m the metrics of
+ * FindPath::eval(sources[i], dests[j]), (q0, q1, q2) the order of mr_params.sort_by
+ * completed to all three metrics (the comparator's own order), ties on all three to the
+ * smallest j (a cell listed twice is won by its first listing).  A destination equal to the
+ * source takes part (metrics 0, via 0xFFFFFFFF) and so wins its group.  The record's first
+ * four words are the matrix record of (i, winner), word for word.  No n_src x n_dst block
+ * exists on the device: a row is n_groups records.
+ * One source with one group of very many destinations is reduced by a single wave (a
+ * group's destinations are never split between waves): such a plan is slower than the
+ * matrix plan of the same lists.
+ * mr_plan_run / _wait / _get_stats / _kernel_ms (the read-off kernel's time) / _destroy apply.
+ * Errors: MR_ERR_INVALID_ARG for a null pointer (but group_of_dst), n_src, n_dst or n_groups
+ * equal to 0, n_groups > n_dst, or a group id >= n_groups (mr_last_error names its position);
+ * MR_ERR_INVALID_INDEX for a source or destination that is not a grid cell; MR_ERR_LIMIT when
+ * plan sources x pitch x 32 B does not fit the device block cache's largest block (16 GiB);
+ * MR_ERR_NO_DEVICE as for the other plans.  The mr_matrix_*, mr_sssp_* and pair-plan
+ * accessors return MR_ERR_INVALID_ARG on a nearest plan, the mr_nearest_* accessors on any
+ * other plan.  MR_ERR_LIMIT for labels holds as stated at mr_status. */
+typedef struct mr_nearest_record {
+    uint32_t legs, money, time_s;
+    uint32_t via;         /* mr_label_record's meaning */
+    uint32_t dst;         /* position j in the caller's list; 0xFFFFFFFF = empty group (all other words 0) */
+    uint32_t reserved[3]; /* 0 */
+} mr_nearest_record;      /* 32 B: four records a 128 B line */
+int mr_nearest_plan_create(const mr_grid *grid, const mr_params *params, const mr_cell_index *sources, uint32_t n_src,
+                           const mr_cell_index *dests, uint32_t n_dst, const uint32_t *group_of_dst, uint32_t n_groups,
+                           mr_plan **out);
+/* the record of the caller's source i and group g at out[i * n_groups + g] (waits);
+ * MR_ERR_CAPACITY if cap_records < n_src * n_groups */
+int mr_nearest_records(mr_plan *plan, mr_nearest_record *out, uint64_t cap_records);
+/* device rows: [plan source][pitch] mr_nearest_record, pitch = n_groups rounded up to 4
+ * records (whole 128 B lines; pad records are zeros).  Waits for the passes enqueued so far;
+ * the next mr_plan_run rewrites the rows */
+int mr_nearest_device_records(mr_plan *plan, void **d_records, uint64_t *bytes);
+int mr_nearest_record_pitch(mr_plan *plan, uint32_t *records_per_row);
+/* row_of_source[i] = device row of the caller's source i (as mr_matrix_source_rows) */
+int mr_nearest_source_rows(const mr_plan *plan, uint32_t *row_of_source, uint32_t n_src);
+/* the winner's label, FindPath::eval(sources[i], dests[record.dst]), rebuilt in full:
+ * MR_OK, MR_NOT_FOUND for an empty group, MR_ERR_CAPACITY (out->n_commands > cap) or an error */
+int mr_nearest_label(mr_plan *plan, uint32_t i, uint32_t g, mr_result *out, mr_command *cmds, uint32_t cap);
+/* The grid's cells with point of interest `poi` (MR_POI_*; MR_POI_NONE: the cells without
+ * one) in row-major order: *n = their number, the first min(cap, *n) written to out (out may
+ * be NULL when cap is 0).  MR_ERR_CAPACITY if *n > cap (*n stays set);
+ * MR_ERR_INVALID_ARG for poi > MR_POI_FORUM or a null grid or n.  Needs no device. */
+int mr_grid_poi_cells(const mr_grid *grid, uint32_t poi, mr_cell_index *out, uint32_t cap, uint32_t *n);
+
 /* ---- misc ---------------------------------------------------------------- */
 uint32_t mr_abi_version(void);
 /* Human-readable description of the last error on this thread. */

@@ -145,6 +145,17 @@ pub struct mr_label_record {
     pub via: u32,
 }
 
+#[repr(C)]
+#[derive(Copy, Clone, Default, Debug)]
+pub struct mr_nearest_record {
+    pub legs: u32,
+    pub money: u32,
+    pub time_s: u32,
+    pub via: u32,
+    pub dst: u32,
+    pub reserved: [u32; 3],
+}
+
 /// Opaque handles.
 pub enum mr_grid {}
 pub enum mr_plan {}
@@ -230,6 +241,18 @@ extern "C" {
     pub fn mr_matrix_source_rows(plan: *const mr_plan, row_of_source: *mut u32, n_src: u32) -> c_int;
     pub fn mr_matrix_label(plan: *mut mr_plan, i: u32, j: u32, out: *mut mr_result, cmds: *mut mr_command,
                            cap: u32) -> c_int;
+
+    // nearest of a set: the best listed destination per source and group
+    pub fn mr_nearest_plan_create(grid: *const mr_grid, params: *const mr_params, sources: *const mr_cell_index,
+                                  n_src: u32, dests: *const mr_cell_index, n_dst: u32, group_of_dst: *const u32,
+                                  n_groups: u32, out: *mut *mut mr_plan) -> c_int;
+    pub fn mr_nearest_records(plan: *mut mr_plan, out: *mut mr_nearest_record, cap_records: u64) -> c_int;
+    pub fn mr_nearest_device_records(plan: *mut mr_plan, d_records: *mut *mut c_void, bytes: *mut u64) -> c_int;
+    pub fn mr_nearest_record_pitch(plan: *mut mr_plan, records_per_row: *mut u32) -> c_int;
+    pub fn mr_nearest_source_rows(plan: *const mr_plan, row_of_source: *mut u32, n_src: u32) -> c_int;
+    pub fn mr_nearest_label(plan: *mut mr_plan, i: u32, g: u32, out: *mut mr_result, cmds: *mut mr_command,
+                            cap: u32) -> c_int;
+    pub fn mr_grid_poi_cells(grid: *const mr_grid, poi: u32, out: *mut mr_cell_index, cap: u32, n: *mut u32) -> c_int;
 
     // misc
     pub fn mr_abi_version() -> u32;

@@ -83,11 +83,19 @@ class mr_plan_stats(C.Structure):
                 ("certified_sources", C.c_uint32), ("lanes_per_source", C.c_uint32)]
 
 
+class mr_nearest_record(C.Structure):
+    _fields_ = [("legs", C.c_uint32), ("money", C.c_uint32), ("time_s", C.c_uint32), ("via", C.c_uint32),
+                ("dst", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+NEAREST_NONE = 0xFFFFFFFF  # mr_nearest_record.dst of an empty group
+
 assert C.sizeof(mr_cell_index) == 8
 assert C.sizeof(mr_cell) == 16
 assert C.sizeof(mr_command) == 40
 assert C.sizeof(mr_result) == 32
 assert C.sizeof(mr_query) == 16
+assert C.sizeof(mr_nearest_record) == 32
 
 
 # ---- value types -------------------------------------------------------------

@@ -854,6 +854,10 @@ struct Core {
             write_matrix(s_idx);
             return;
         }
+        if (a->all_mode == kAllNearest) {
+            write_nearest(s_idx);
+            return;
+        }
         if (a->all_mode) {
             write_all(s_idx);
             return;
@@ -896,6 +900,103 @@ struct Core {
             row[j] = make_uint4(o.legs, o.money, o.time_s, o.via);
         }
         if (threadIdx.x == 0) a->src_state[s_idx] = 2;
+    }
+    // nearest plans (DESIGN.md section 3b''): the label table and one 32 B record per destination
+    // group — the least (metrics in comparator order, sorted index) over the group's
+    // destinations, each the expansion of the cell word write_all would store.  The workgroup
+    // walks the chunk table (KArgs::nr_chunk) four chunks a step, a wave a chunk: the wave narrows
+    // its chunk to one key on the DPP network and leaves it in LDS (`dst`, which no
+    // all-destinations mode uses), and thread 0 folds the step's keys in chunk order into the
+    // running best of the current group; a group's record is stored when the next group begins
+    // (empty groups: dst = all ones, the other words 0; pad records of the row: zeros).
+    __device__ __forceinline__ void write_nearest(uint32_t s_idx) const {
+        const DevParams &p = P;
+        const uint32_t T = p.NS + 1;
+        const unsigned long long tb = (unsigned long long)s_idx * T;
+        for (uint32_t t = threadIdx.x; t <= p.NS; t += kBS) {
+            a->out_tab[tb + t] = R[t];
+            a->out_lex[tb + t] = kNone32;
+        }
+        constexpr uint32_t nw = kBS / 64, kW = 8;  // per wave: valid, the key's four words, via, group
+        static_assert(nw * kW * 4 <= 64 * 4, "write_nearest: the waves' keys must fit the dst area (lds_layout: 64 words)");
+        const uint32_t lane = lane_id(), wv = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
+        const uint32_t ng = a->nr_ngroups, nc = a->nr_nchunk, pitch = a->mx_pitch;
+        uint4 *row = a->mx_rows + 2ull * (unsigned long long)s_idx * pitch;
+        const FfRatio ff{p.ff_num, p.ff_den};
+        const uint32_t q0 = p.perm[0], q1 = p.perm[1], q2 = p.perm[2];
+        uint32_t *red = dst;
+        // thread 0: the running best of group `cur`
+        uint32_t cur = 0, b0 = kNone32, b1 = kNone32, b2 = kNone32, b3 = kNone32, bvia = 0;
+        const auto flush = [&](uint32_t upto) {
+            for (; cur < upto; ++cur) {
+                uint4 lo = make_uint4(0u, 0u, 0u, 0u), hi = make_uint4(kNone32, 0u, 0u, 0u);
+                if (b3 != kNone32) {
+                    lo = make_uint4(q0 == 0 ? b0 : (q1 == 0 ? b1 : b2), q0 == 1 ? b0 : (q1 == 1 ? b1 : b2),
+                                    q0 == 2 ? b0 : (q1 == 2 ? b1 : b2), bvia);
+                    hi.x = a->nr_pos[b3];
+                }
+                row[2ull * cur] = lo;
+                row[2ull * cur + 1] = hi;
+                b0 = b1 = b2 = b3 = kNone32;
+            }
+        };
+        for (uint32_t c0 = 0; c0 < nc; c0 += nw) {
+            const uint32_t c = c0 + wv;
+            if (c < nc) {
+                const uint4 ch = a->nr_chunk[c];
+                bool cand = lane < ch.z;
+                mr_label_record o{0u, 0u, 0u, 0u};
+                if (cand) {
+                    const uint32_t xy = a->mx_dst[ch.y + lane].x;
+                    const int x = int(short(xy & 0xFFFFu)), y = int(short(xy >> 16));
+                    const uint32_t v = uint32_t(y + int(p.H)) * p.S + uint32_t(x + int(p.H));
+                    if (!expand_word(cell_word(v), T, ff, [&](uint32_t t, uint32_t q) { return R[t].m[q]; }, o))
+                        flag(kErrChain);
+                }
+                const auto om = [&](uint32_t q) { return q == 0 ? o.legs : (q == 1 ? o.money : o.time_s); };
+                const uint32_t m0 = wave_min_u32(cand ? om(q0) : kNone32);
+                cand = cand && om(q0) == m0;
+                const uint32_t m1 = wave_min_u32(cand ? om(q1) : kNone32);
+                cand = cand && om(q1) == m1;
+                const uint32_t m2 = wave_min_u32(cand ? om(q2) : kNone32);
+                cand = cand && om(q2) == m2;
+                const unsigned long long cm = __ballot(cand);  // the first of them: the least sorted index
+                if (cm != 0 && lane == uint32_t(__ffsll((long long)cm) - 1)) {
+                    uint32_t *e = red + wv * kW;
+                    e[1] = m0;
+                    e[2] = m1;
+                    e[3] = m2;
+                    e[4] = ch.y + lane;
+                    e[5] = o.via;
+                    e[6] = ch.x;
+                }
+                if (lane == 0) red[wv * kW] = cm != 0 ? 1u : 0u;
+            } else if (lane == 0) {
+                red[wv * kW] = 0u;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                for (uint32_t w = 0; w < nw; ++w) {
+                    const uint32_t *e = red + w * kW;
+                    if (!e[0]) continue;
+                    if (e[6] != cur) flush(e[6]);
+                    // (chunks come in sorted order: equal metrics keep the earlier chunk's winner)
+                    if (b3 == kNone32 || e[1] < b0 || (e[1] == b0 && (e[2] < b1 || (e[2] == b1 && e[3] < b2)))) {
+                        b0 = e[1];
+                        b1 = e[2];
+                        b2 = e[3];
+                        b3 = e[4];
+                        bvia = e[5];
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            flush(ng);
+            for (uint32_t k = 2u * ng; k < 2u * pitch; ++k) row[k] = make_uint4(0u, 0u, 0u, 0u);
+            a->src_state[s_idx] = 2;
+        }
     }
     // all-destinations mode: the label table and a cell word for every cell (CellWord:
     // the settled state word's walk (b, k) as it stands)

@@ -250,9 +250,22 @@ struct KArgs {
     uint4 *mx_rows;
     uint32_t mx_ndst;
     uint32_t mx_pitch;
+    // nearest plans (all_mode == kAllNearest, DESIGN.md section 3b''): per source a row of
+    // mx_pitch 32 B records (mr_nearest_record; two uint4 of mx_rows each), record g the best
+    // destination of group g.  mx_dst holds the mx_ndst destinations stable-sorted by group,
+    // nr_pos[k] the caller's position of sorted destination k.  nr_chunk[c] = {group, first
+    // sorted destination, count <= 64, 0}: the chunks in sorted order, none spans two groups;
+    // nr_gstart[g] = the first chunk of group g (nr_ngroups + 1 entries, the last = nr_nchunk).
+    // mx_pitch = nr_ngroups rounded up to 4 records (a 128 B line)
+    const uint32_t *nr_pos;
+    const uint4 *nr_chunk;
+    const uint32_t *nr_gstart;
+    uint32_t nr_ngroups;
+    uint32_t nr_nchunk;
 };
-// KArgs::all_mode: a cell word per (source, cell), or a record per (source, listed destination)
-constexpr uint32_t kAllCells = 1u, kAllMatrix = 2u;
+// KArgs::all_mode: a cell word per (source, cell), a record per (source, listed destination),
+// or a record per (source, group of listed destinations)
+constexpr uint32_t kAllCells = 1u, kAllMatrix = 2u, kAllNearest = 3u;
 constexpr uint32_t kLaneWinBits = 5u, kLaneWinNone = 31u, kLaneRegNone = 255u;
 // cert_redo[slot]: kRedoFill — promoted specials: the closed form again, both checks and the
 // repair; kRedoSweep — specials the last check demoted: the repair from the current words

@@ -39,6 +39,8 @@ int hub_blocks_per_cu(const uint32_t perm[3], uint32_t spw, bool nonlin, uint32_
 int fill_blocks_per_cu(const uint32_t perm[3]);
 hipError_t launch_matrix(const KArgs *d_args, const uint32_t perm[3], uint32_t gx, hipStream_t stream);
 int matrix_blocks_per_cu(const uint32_t perm[3]);
+hipError_t launch_nearest(const KArgs *d_args, const uint32_t perm[3], uint32_t gx, hipStream_t stream);
+int nearest_blocks_per_cu(const uint32_t perm[3]);
 hipError_t launch_hub_fill(const KArgs *hub_args, const KArgs *fill_args, const uint32_t perm[3], uint32_t spw,
                            uint32_t hub_blocks, uint32_t fill_blocks, uint32_t lds_bytes, hipStream_t stream);
 int hub_fill_blocks_per_cu(const uint32_t perm[3], uint32_t spw, uint32_t lds_bytes);
@@ -1594,6 +1596,9 @@ struct mr_plan {
     // a matrix plan: an all-destinations plan (all_mode) that writes a record per listed
     // destination (Matrix below) instead of a cell word per cell
     bool matrix = false;
+    // a nearest plan: a matrix plan (matrix is set too: no cell words, serial launches, one
+    // slot) whose rows hold one record per destination group (Nearest below)
+    bool nearest = false;
     bool grid_in_lds = false;
     uint32_t algo = kAlgoGeneric;
     uint32_t blocks = 0, cus = 256;
@@ -1666,6 +1671,16 @@ struct mr_plan {
         std::vector<uint32_t> dst_v;
         uint32_t n_src = 0, n_dst = 0, pitch = 0, per_cu = 1;
     } mx;
+    // nearest plans: mx.dst holds the destinations stable-sorted by group (mx.dst_v stays in
+    // the caller's order), mx.rows two uint4 a record, mx.pitch = n_groups rounded up to 4;
+    // the caller's groups, the sorted destinations' caller positions, the chunk table and the
+    // groups' first chunks (KArgs::nr_*)
+    struct Nearest {
+        std::vector<uint32_t> group;
+        DevBuf<uint32_t> pos, gstart;
+        DevBuf<uint4> chunk;
+        uint32_t n_groups = 0;
+    } nr;
     struct Hub {
         uint32_t n_lane = 0;               // sources on the lane kernel; the rest on hub_kernel
         uint32_t lane_g = 0;               // > 0: the n_lane sources run G lanes each (hub_group_kernel)
@@ -2452,7 +2467,7 @@ static int plan_all_outputs(mr_plan *pl, uint32_t n) {
     if ((!pl->matrix && pl->out.rec.alloc(ns * hp.p.S * pitch) != hipSuccess) || k.tab.alloc(ns * T) != hipSuccess ||
         k.lex.alloc(ns * T) != hipSuccess || k.sstate.alloc(ns) != hipSuccess)
         return fail(MR_ERR_DEVICE, "hipMalloc all-destinations outputs");
-    ka.all_mode = pl->matrix ? kAllMatrix : kAllCells;
+    ka.all_mode = pl->nearest ? kAllNearest : pl->matrix ? kAllMatrix : kAllCells;
     ka.out_rec = pl->out.rec.get();
     ka.early_exit_max = 0;  // every cell must settle
     pl->src_of_input.assign(n, kNone32);
@@ -2495,6 +2510,65 @@ static int plan_matrix_outputs(mr_plan *pl) {
     ka.mx_ndst = m.n_dst;
     ka.mx_pitch = m.pitch;
     m.per_cu = uint32_t(std::max(1, matrix_blocks_per_cu(hp.p.perm)));
+    return MR_OK;
+}
+
+// nearest plans: the destinations resolved as plan_matrix_outputs does and stable-sorted by
+// group (so the smallest sorted index of a group is the caller's smallest position), their
+// caller positions, the chunk table {group, first sorted destination, count <= 64} whose
+// chunks never span two groups, the groups' first chunks, and the record rows,
+// [plan source][pitch] of 32 B, pitch = n_groups rounded up to whole 128 B lines
+static int plan_nearest_outputs(mr_plan *pl) {
+    const HostPlan &hp = pl->hp;
+    KArgs &ka = pl->ka;
+    mr_plan::Matrix &m = pl->mx;
+    mr_plan::Nearest &nr = pl->nr;
+    const mr_grid *g = pl->grid;
+    m.n_dst = uint32_t(m.dst_v.size());
+    const uint32_t ng = nr.n_groups;
+    const uint64_t pitch = (uint64_t(ng) + 3) / 4 * 4, ns = std::max<uint32_t>(ka.nsrc, 1);
+    if (pitch > 0xFFFFFFFFull || ns * pitch > kMatrixMaxBytes / sizeof(mr_nearest_record))
+        return fail(MR_ERR_LIMIT, "nearest plan: " + std::to_string(ns) + " sources x " + std::to_string(pitch) +
+                                      " records of 32 B exceed the device block cache's largest block");
+    m.pitch = uint32_t(pitch);
+    std::vector<std::pair<uint32_t, uint32_t>> spv;  // (cell, table index) of the specials
+    for (uint32_t t = 1; t <= hp.p.NS; ++t) spv.push_back({hp.sp[t].v, t});
+    std::sort(spv.begin(), spv.end());
+    std::vector<uint32_t> pos(m.n_dst);
+    for (uint32_t j = 0; j < m.n_dst; ++j) pos[j] = j;
+    std::stable_sort(pos.begin(), pos.end(), [&](uint32_t x, uint32_t y) { return nr.group[x] < nr.group[y]; });
+    std::vector<uint2> d(m.n_dst);
+    std::vector<uint4> chunk;
+    std::vector<uint32_t> gstart(size_t(ng) + 1, 0u);
+    for (uint32_t k = 0, gi = 0; k < m.n_dst;) {
+        const uint32_t grp = nr.group[pos[k]];
+        uint32_t e = k;
+        while (e < m.n_dst && nr.group[pos[e]] == grp) ++e;
+        for (; gi <= grp; ++gi) gstart[gi] = uint32_t(chunk.size());  // (the empty groups before it: no chunks)
+        for (uint32_t f = k; f < e; f += 64) chunk.push_back(make_uint4(grp, f, std::min(64u, e - f), 0u));
+        k = e;
+        if (k == m.n_dst)
+            for (; gi <= ng; ++gi) gstart[gi] = uint32_t(chunk.size());
+    }
+    for (uint32_t k = 0; k < m.n_dst; ++k) {
+        const uint32_t v = m.dst_v[pos[k]];
+        const auto it = std::lower_bound(spv.begin(), spv.end(), std::make_pair(v, 0u));
+        d[k].x = (uint32_t(g->gx(v)) & 0xFFFFu) | (uint32_t(g->gy(v)) << 16);
+        d[k].y = it != spv.end() && it->first == v ? (kViaSpecial | it->second) : (v & ~kViaSpecial);
+    }
+    if (upload(m.dst, d) != hipSuccess || upload(nr.pos, pos) != hipSuccess || upload(nr.chunk, chunk) != hipSuccess ||
+        upload(nr.gstart, gstart) != hipSuccess || m.rows.alloc(size_t(ns * pitch * 2)) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "hipMalloc nearest outputs");
+    ka.mx_dst = m.dst.get();
+    ka.mx_rows = m.rows.get();
+    ka.mx_ndst = m.n_dst;
+    ka.mx_pitch = m.pitch;
+    ka.nr_pos = nr.pos.get();
+    ka.nr_chunk = nr.chunk.get();
+    ka.nr_gstart = nr.gstart.get();
+    ka.nr_ngroups = ng;
+    ka.nr_nchunk = uint32_t(chunk.size());
+    m.per_cu = uint32_t(std::max(1, nearest_blocks_per_cu(hp.p.perm)));
     return MR_OK;
 }
 
@@ -2774,7 +2848,8 @@ static int plan_overlap(mr_plan *pl) {
 }
 
 static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *qs, uint32_t n, uint32_t max_cmds,
-                       mr_plan **out, bool all_mode = false, std::vector<uint32_t> *matrix_dst = nullptr) {
+                       mr_plan **out, bool all_mode = false, std::vector<uint32_t> *matrix_dst = nullptr,
+                       std::vector<uint32_t> *nearest_group = nullptr, uint32_t n_groups = 0) {
     if (!out || (n && !qs)) return fail(MR_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     if (!mr_device_available()) return fail(MR_ERR_NO_DEVICE, "no gfx950 device visible (no CPU fallback)");
@@ -2787,6 +2862,11 @@ static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *q
     pl->all_mode = all_mode;
     pl->matrix = matrix_dst != nullptr;
     if (matrix_dst) pl->mx.dst_v = std::move(*matrix_dst);
+    pl->nearest = matrix_dst && nearest_group;
+    if (pl->nearest) {
+        pl->nr.group = std::move(*nearest_group);
+        pl->nr.n_groups = n_groups;
+    }
     HostPlan &hp = pl->hp;
     int st = build_plan(g, prm, qs, n, max_cmds, hp, !all_mode);
     if (st == MR_OK && hp.dev_grouped) {  // the batch grouped on the device (counts back)
@@ -2807,7 +2887,7 @@ static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *q
     if (pl->stream.create() != hipSuccess) return fail(MR_ERR_DEVICE, "stream");
     plan_base_args(pl.get(), n);
     if (all_mode && (st = plan_all_outputs(pl.get(), n))) return st;
-    if (pl->matrix && (st = plan_matrix_outputs(pl.get()))) return st;
+    if (pl->matrix && (st = pl->nearest ? plan_nearest_outputs(pl.get()) : plan_matrix_outputs(pl.get()))) return st;
     if (hp.hub && ((st = plan_hub(pl.get())) || (st = plan_cert(pl.get())) || (st = plan_lane(pl.get())))) return st;
     if ((st = plan_lane_memo(pl.get()))) return st;
     plan_diag(pl.get());
@@ -2911,6 +2991,11 @@ static hipError_t run_all(mr_plan *pl, hipStream_t s) {
         gx = resident_grid((items + 3) / 4, uint64_t(pl->mx.per_cu) * pl->cus);
         if (const char *e = std::getenv("MR_MATRIX_GX")) gx = uint32_t(std::max(1, std::atoi(e)));
     }
+    if (pl->nearest) {  // (source, group) items, one per wave; MR_NEAREST_GX fixes the grid
+        const uint64_t items = uint64_t(pl->ka.nsrc) * pl->nr.n_groups;
+        gx = resident_grid((items + 3) / 4, uint64_t(pl->mx.per_cu) * pl->cus);
+        if (const char *e = std::getenv("MR_NEAREST_GX")) gx = uint32_t(std::max(1, std::atoi(e)));
+    }
     const hipStream_t hs = pl->overlap ? pl->hub_stream.get() : s;
     hipError_t e = launch_hub_plan(pl, k.args.get(), hs);
     if (e == hipSuccess && pl->overlap &&
@@ -2920,8 +3005,9 @@ static hipError_t run_all(mr_plan *pl, hipStream_t s) {
     Event f0;
     if (e == hipSuccess) f0 = fill_start(s);
     if (e == hipSuccess)
-        e = pl->matrix ? launch_matrix(k.args_fill.get(), pl->ka.p.perm, gx, s)
-                       : launch_fill(k.args_fill.get(), pl->ka.p.perm, gx, 1, s);
+        e = pl->nearest  ? launch_nearest(k.args_fill.get(), pl->ka.p.perm, gx, s)
+            : pl->matrix ? launch_matrix(k.args_fill.get(), pl->ka.p.perm, gx, s)
+                         : launch_fill(k.args_fill.get(), pl->ka.p.perm, gx, 1, s);
     // the slot's tables are free again once this fill has read them
     if (e == hipSuccess && pl->overlap && hipEventRecord(k.ev_fill.get(), s) != hipSuccess) e = hipErrorUnknown;
     pl->timed_fill.push_back({std::move(f0), nullptr, false});  // one per pass (f0 may be empty), as in `timed`
@@ -3282,7 +3368,8 @@ extern "C" int mr_plan_wait(mr_plan *pl, void *stream) {
 
 extern "C" int mr_plan_device_outputs(mr_plan *pl, void **d_results, uint64_t *rb, void **d_commands, uint64_t *cb) {
     if (!pl) return fail(MR_ERR_INVALID_ARG, "null plan");
-    if (pl->matrix) return fail(MR_ERR_INVALID_ARG, "device_outputs: not a query plan (mr_matrix_device_records)");
+    if (pl->matrix) return fail(MR_ERR_INVALID_ARG, pl->nearest ? "device_outputs: not a query plan (mr_nearest_device_records)"
+                                                        : "device_outputs: not a query plan (mr_matrix_device_records)");
     // the pointers are handed out once the plan's passes so far have finished, so a
     // raw read right after this call sees whole records (mr_plan_wait orders a stream
     // instead of the host)
@@ -3587,7 +3674,7 @@ static bool plan_fetch_wire(mr_plan *pl, mr_result *results, mr_command *pool, u
 
 extern "C" int mr_plan_fetch(mr_plan *pl, mr_result *results, mr_command *pool, uint64_t pool_cap) {
     if (!pl || (pl->hp.nq && !results)) return fail(MR_ERR_INVALID_ARG, "null argument");
-    if (pl->matrix) return fail(MR_ERR_INVALID_ARG, "fetch: not a query plan (mr_matrix_records)");
+    if (pl->matrix) return fail(MR_ERR_INVALID_ARG, pl->nearest ? "fetch: not a query plan (mr_nearest_records)" : "fetch: not a query plan (mr_matrix_records)");
     {
         int ret = MR_OK;
         if (plan_fetch_wire(pl, results, pool, pool_cap, ret)) return ret;
@@ -4263,7 +4350,7 @@ extern "C" int mr_matrix_plan_create(const mr_grid *g, const mr_params *prm, con
 
 // a matrix plan whose last pass raised no device error (waits for the plan)
 static int matrix_plan(mr_plan *pl) {
-    if (!pl || !pl->matrix) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     uint32_t flags = 0;
     return check_device_errors(pl, flags);
 }
@@ -4292,7 +4379,7 @@ extern "C" int mr_matrix_records(mr_plan *pl, mr_label_record *out, uint64_t cap
 }
 
 extern "C" int mr_matrix_device_records(mr_plan *pl, void **d_records, uint64_t *bytes) {
-    if (!pl || !pl->matrix) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // whole records behind the pointer
     if (d_records) *d_records = pl->mx.rows.get();
     if (bytes) *bytes = uint64_t(pl->ka.nsrc) * pl->mx.pitch * sizeof(mr_label_record);
@@ -4300,14 +4387,14 @@ extern "C" int mr_matrix_device_records(mr_plan *pl, void **d_records, uint64_t 
 }
 
 extern "C" int mr_matrix_record_pitch(mr_plan *pl, uint32_t *records_per_row) {
-    if (!pl || !pl->matrix) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     if (!records_per_row) return fail(MR_ERR_INVALID_ARG, "null output");
     *records_per_row = pl->mx.pitch;
     return MR_OK;
 }
 
 extern "C" int mr_matrix_source_rows(const mr_plan *pl, uint32_t *row_of_source, uint32_t n_src) {
-    if (!pl || !pl->matrix) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     if (n_src && !row_of_source) return fail(MR_ERR_INVALID_ARG, "null output");
     for (uint32_t i = 0; i < n_src; ++i) row_of_source[i] = i < pl->src_of_input.size() ? pl->src_of_input[i] : kNone32;
     return MR_OK;
@@ -4347,5 +4434,148 @@ extern "C" int mr_matrix_label(mr_plan *pl, uint32_t i, uint32_t j, mr_result *r
     const CmdScale cs = cmd_scale(pl->hp);
     for (size_t q = 0; q < seq.size(); ++q)
         if (!expand_cmd(pl->grid, cs, seq[q], cmds[q])) return fail(MR_ERR_DEVICE, "command names no cell");
+    return MR_OK;
+}
+
+// ------------------------------------------------------------ nearest of a set
+extern "C" int mr_nearest_plan_create(const mr_grid *g, const mr_params *prm, const mr_cell_index *sources, uint32_t n_src,
+                                      const mr_cell_index *dests, uint32_t n_dst, const uint32_t *group_of_dst,
+                                      uint32_t n_groups, mr_plan **out) {
+    if (!g || !prm || !out || !sources || !dests) return fail(MR_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!n_src || !n_dst || !n_groups)
+        return fail(MR_ERR_INVALID_ARG, "a nearest plan needs at least one source, one destination and one group");
+    if (n_groups > n_dst) return fail(MR_ERR_INVALID_ARG, "a nearest plan cannot have more groups than destinations");
+    std::vector<uint32_t> grp(n_dst, 0u);
+    for (uint32_t j = 0; group_of_dst && j < n_dst; ++j) {
+        if (group_of_dst[j] >= n_groups)
+            return fail(MR_ERR_INVALID_ARG, "group of destination " + std::to_string(j) + " is not below n_groups");
+        grp[j] = group_of_dst[j];
+    }
+    if (!mr_device_available()) return fail(MR_ERR_NO_DEVICE, "no gfx950 device visible (no CPU fallback)");
+    std::vector<uint32_t> dv(n_dst);
+    for (uint32_t i = 0; i < n_src; ++i) {
+        uint32_t v;
+        if (!g->find(sources[i], v)) return fail(MR_ERR_INVALID_INDEX, "source " + std::to_string(i) + " is not a grid cell");
+    }
+    for (uint32_t j = 0; j < n_dst; ++j)
+        if (!g->find(dests[j], dv[j]))
+            return fail(MR_ERR_INVALID_INDEX, "destination " + std::to_string(j) + " is not a grid cell");
+    std::vector<mr_query> qs(n_src);
+    for (uint32_t i = 0; i < n_src; ++i) qs[i].from = qs[i].to = sources[i];
+    const int st = plan_create(g, prm, qs.data(), n_src, 16, out, true, &dv, &grp, n_groups);
+    if (st == MR_OK) (*out)->mx.n_src = n_src;
+    return st;
+}
+
+// a nearest plan whose last pass raised no device error (waits for the plan)
+static int nearest_plan(mr_plan *pl) {
+    if (!pl || !pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a nearest plan");
+    uint32_t flags = 0;
+    return check_device_errors(pl, flags);
+}
+
+extern "C" int mr_nearest_records(mr_plan *pl, mr_nearest_record *out, uint64_t cap_records) {
+    if (int st = nearest_plan(pl)) return st;
+    if (!out) return fail(MR_ERR_INVALID_ARG, "null output");
+    const mr_plan::Matrix &m = pl->mx;
+    const uint32_t ng = pl->nr.n_groups;
+    if (cap_records < uint64_t(m.n_src) * ng)
+        return fail(MR_ERR_CAPACITY, "mr_nearest_records: output shorter than n_src x n_groups");
+    // as mr_matrix_records: one copy when the rows are the caller's table, else a row at a time
+    const mr_nearest_record *rows = reinterpret_cast<const mr_nearest_record *>(m.rows.get());
+    bool in_order = m.pitch == ng;
+    for (uint32_t i = 0; i < m.n_src && in_order; ++i) in_order = pl->src_of_input[i] == i;
+    hipError_t e = hipSuccess;
+    if (in_order) {
+        e = hipMemcpy(out, rows, size_t(m.n_src) * ng * sizeof(mr_nearest_record), hipMemcpyDeviceToHost);
+    } else {
+        for (uint32_t i = 0; i < m.n_src && e == hipSuccess; ++i)
+            e = hipMemcpy(out + size_t(i) * ng, rows + size_t(pl->src_of_input[i]) * m.pitch,
+                          size_t(ng) * sizeof(mr_nearest_record), hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) return fail(MR_ERR_DEVICE, std::string("copy nearest records: ") + hipGetErrorString(e));
+    return MR_OK;
+}
+
+extern "C" int mr_nearest_device_records(mr_plan *pl, void **d_records, uint64_t *bytes) {
+    if (!pl || !pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a nearest plan");
+    if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // whole records behind the pointer
+    if (d_records) *d_records = pl->mx.rows.get();
+    if (bytes) *bytes = uint64_t(pl->ka.nsrc) * pl->mx.pitch * sizeof(mr_nearest_record);
+    return MR_OK;
+}
+
+extern "C" int mr_nearest_record_pitch(mr_plan *pl, uint32_t *records_per_row) {
+    if (!pl || !pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a nearest plan");
+    if (!records_per_row) return fail(MR_ERR_INVALID_ARG, "null output");
+    *records_per_row = pl->mx.pitch;
+    return MR_OK;
+}
+
+extern "C" int mr_nearest_source_rows(const mr_plan *pl, uint32_t *row_of_source, uint32_t n_src) {
+    if (!pl || !pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a nearest plan");
+    if (n_src && !row_of_source) return fail(MR_ERR_INVALID_ARG, "null output");
+    for (uint32_t i = 0; i < n_src; ++i) row_of_source[i] = i < pl->src_of_input.size() ? pl->src_of_input[i] : kNone32;
+    return MR_OK;
+}
+
+extern "C" int mr_nearest_label(mr_plan *pl, uint32_t i, uint32_t g, mr_result *res, mr_command *cmds, uint32_t cap) {
+    if (int st = nearest_plan(pl)) return st;
+    if (!res) return fail(MR_ERR_INVALID_ARG, "null result");
+    const mr_plan::Matrix &m = pl->mx;
+    if (i >= m.n_src || g >= pl->nr.n_groups) return fail(MR_ERR_INVALID_ARG, "nearest index");
+    const uint32_t si = pl->src_of_input[i];
+    mr_nearest_record win;
+    if (hipMemcpy(&win, reinterpret_cast<const mr_nearest_record *>(m.rows.get()) + size_t(si) * m.pitch + g, sizeof(win),
+                  hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "copy label");
+    std::memset(res, 0, sizeof(*res));
+    if (win.dst == kNone32) {  // an empty group
+        res->status = MR_NOT_FOUND;
+        return MR_NOT_FOUND;
+    }
+    if (win.dst >= m.n_dst || pl->nr.group[win.dst] != g) return fail(MR_ERR_DEVICE, "record names no destination of its group");
+    const uint32_t w = m.dst_v[win.dst];
+    const mr_label_record got{win.legs, win.money, win.time_s, win.via};
+    std::vector<Rec> tab;
+    if (int st = sssp_table(pl, si, tab)) return st;
+    // the cell word the record expands (mr_matrix_label)
+    CellWord word = got.via;
+    if (got.via != kViaSource && !(got.via & kViaSpecial)) {
+        if (got.via >= tab.size() || got.legs - tab[got.via].m[0] > kStKMask)
+            return fail(MR_ERR_DEVICE, "record names no boundary");
+        word = (got.via << kStBShift) | (got.legs - tab[got.via].m[0]);
+    }
+    mr_label_record rec;
+    std::vector<OutCmd> seq;
+    if (int st = sssp_expand(pl, si, tab, w, word, rec, seq)) return st;
+    if (std::memcmp(&rec, &got, sizeof(rec)) != 0) return fail(MR_ERR_DEVICE, "record is not its cell word's expansion");
+    res->legs = rec.legs;
+    res->money = rec.money;
+    res->time_s = int64_t(rec.time_s);
+    res->n_commands = uint32_t(seq.size());
+    if (seq.size() > cap || (!cmds && !seq.empty())) {
+        res->status = MR_ERR_CAPACITY;
+        return MR_ERR_CAPACITY;
+    }
+    const CmdScale cs = cmd_scale(pl->hp);
+    for (size_t q = 0; q < seq.size(); ++q)
+        if (!expand_cmd(pl->grid, cs, seq[q], cmds[q])) return fail(MR_ERR_DEVICE, "command names no cell");
+    return MR_OK;
+}
+
+extern "C" int mr_grid_poi_cells(const mr_grid *g, uint32_t poi, mr_cell_index *out, uint32_t cap, uint32_t *n) {
+    if (!g || !n || (cap && !out)) return fail(MR_ERR_INVALID_ARG, "null argument");
+    *n = 0;
+    if (poi > MR_POI_FORUM) return fail(MR_ERR_INVALID_ARG, "mr_grid_poi_cells: poi is not an MR_POI_* value");
+    uint32_t k = 0;
+    for (uint32_t v = 0; v < g->V; ++v) {
+        if (g->poi[v] != poi) continue;
+        if (k < cap) out[k] = g->idx[v];
+        ++k;
+    }
+    *n = k;
+    if (k > cap) return fail(MR_ERR_CAPACITY, "mr_grid_poi_cells: " + std::to_string(k) + " cells, room for " + std::to_string(cap));
     return MR_OK;
 }

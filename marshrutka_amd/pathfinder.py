@@ -32,6 +32,8 @@ EXPORTED_SYMBOLS = [
     "mr_sssp_plan_create", "mr_sssp_records", "mr_sssp_device_records", "mr_sssp_record_pitch", "mr_sssp_device_tables", "mr_sssp_label", "mr_sssp_labels", "mr_plan_fill_ms",
     "mr_matrix_plan_create", "mr_matrix_records", "mr_matrix_device_records", "mr_matrix_record_pitch",
     "mr_matrix_source_rows", "mr_matrix_label",
+    "mr_nearest_plan_create", "mr_nearest_records", "mr_nearest_device_records", "mr_nearest_record_pitch",
+    "mr_nearest_source_rows", "mr_nearest_label", "mr_grid_poi_cells",
 ]
 
 
@@ -164,6 +166,23 @@ def lib():
         L.mr_matrix_label.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(mr_result), C.POINTER(mr_command),
                                       C.c_uint32]
         L.mr_matrix_label.restype = C.c_int
+        L.mr_nearest_plan_create.argtypes = [vp, C.POINTER(mr_params), C.POINTER(mr_cell_index), C.c_uint32,
+                                             C.POINTER(mr_cell_index), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
+                                             C.POINTER(vp)]
+        L.mr_nearest_plan_create.restype = C.c_int
+        L.mr_nearest_records.argtypes = [vp, vp, C.c_uint64]
+        L.mr_nearest_records.restype = C.c_int
+        L.mr_nearest_device_records.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.mr_nearest_device_records.restype = C.c_int
+        L.mr_nearest_record_pitch.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.mr_nearest_record_pitch.restype = C.c_int
+        L.mr_nearest_source_rows.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint32]
+        L.mr_nearest_source_rows.restype = C.c_int
+        L.mr_nearest_label.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(mr_result), C.POINTER(mr_command),
+                                       C.c_uint32]
+        L.mr_nearest_label.restype = C.c_int
+        L.mr_grid_poi_cells.argtypes = [vp, C.c_uint32, C.POINTER(mr_cell_index), C.c_uint32, C.POINTER(C.c_uint32)]
+        L.mr_grid_poi_cells.restype = C.c_int
         _lib = L
     return _lib
 
@@ -266,6 +285,18 @@ class MapGrid:
             raise EngineError(st, last_error())
         return nreg.value, ms.value, out
 
+    def poi_cells(self, poi: int) -> List[CellIndex]:
+        """The grid's cells with point of interest `poi` (abi.POI_*), in row-major order."""
+        n = C.c_uint32()
+        st = lib().mr_grid_poi_cells(self.handle, poi, None, 0, C.byref(n))
+        if st not in (MR_OK, MR_ERR_CAPACITY):
+            raise EngineError(st, last_error())
+        out = (mr_cell_index * max(1, n.value))()
+        st = lib().mr_grid_poi_cells(self.handle, poi, out, n.value, C.byref(n))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return [CellIndex(c.kind, c.sub, c.x, c.y) for c in out[: n.value]]
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h and _lib is not None:
@@ -325,6 +356,36 @@ class FindPath:
         plan = MatrixPlan(self.grid, self.params(), sources, dests)
         plan.run()
         return plan.records()
+
+    def eval_nearest(self, sources: Sequence[CellIndex], dests: Sequence[CellIndex], groups: Optional[Sequence[int]] = None):
+        """The best destination of each group for every source after one pass of a NearestPlan:
+        a (n_src, n_groups, 5) uint32 array of legs, money, time, via, dst (the winner's position
+        in `dests`; 0xFFFFFFFF and zeros for an empty group)."""
+        plan = NearestPlan(self.grid, self.params(), sources, dests, groups)
+        plan.run()
+        return plan.records()
+
+    def eval_nearest_poi(self, sources: Sequence[CellIndex], pois: Sequence[int] = (abi.POI_FOUNTAIN, abi.POI_FORUM)):
+        """The nearest cell of each point-of-interest kind for every source, one group a kind:
+        (records as eval_nearest gives them, the destination list the records' dst indexes).
+        A kind the map lacks is an empty group."""
+        import numpy as np
+        dests: List[CellIndex] = []
+        groups: List[int] = []
+        present: List[int] = []  # the kinds the map has: the plan's groups (a plan takes no more groups than destinations)
+        for g, poi in enumerate(pois):
+            cells = self.grid.poi_cells(poi)
+            if cells:
+                dests += cells
+                groups += [len(present)] * len(cells)
+                present.append(g)
+        out = np.zeros((len(sources), len(pois), 5), dtype=np.uint32)
+        out[:, :, 4] = abi.NEAREST_NONE
+        if dests:
+            plan = NearestPlan(self.grid, self.params(), sources, dests, groups, n_groups=len(present))
+            plan.run()
+            out[:, present] = plan.records()
+        return out, dests
 
     def eval_batch_raw(self, pairs: Sequence[Tuple[CellIndex, CellIndex]]):
         n = len(pairs)
@@ -782,3 +843,89 @@ class MatrixPlan(Plan):
 
     def fetch(self):
         raise NotImplementedError("matrix plans: use records() / label()")
+
+
+class NearestPlan(Plan):
+    """Nearest of a set: run() keeps, for every source and destination group, the 32 B record of
+    the group's best destination (the least metrics in the parameters' order, ties to the smallest
+    position in `dests`) and which destination it was; label(i, g) rebuilds its full TotalCost."""
+
+    def __init__(self, grid: MapGrid, params: Params, sources: Sequence[CellIndex], dests: Sequence[CellIndex],
+                 groups: Optional[Sequence[int]] = None, n_groups: Optional[int] = None):
+        self.grid = grid
+        self.n = len(sources)
+        self.n_dst = len(dests)
+        self.sources = list(sources)
+        self.dests = list(dests)
+        self.groups = None if groups is None else [int(g) for g in groups]
+        if self.groups is not None and len(self.groups) != self.n_dst:
+            raise EngineError(abi.MR_ERR_INVALID_ARG, "groups: one id per destination")
+        if n_groups is None:
+            n_groups = 1 if self.groups is None else max(self.groups, default=0) + 1
+        self.n_groups = n_groups
+        self._p = params.to_c()
+        garr = None
+        if self.groups is not None:
+            if any(g < 0 or g > 0xFFFFFFFF for g in self.groups):
+                raise EngineError(abi.MR_ERR_INVALID_ARG, "groups: ids are unsigned 32-bit")
+            garr = (C.c_uint32 * max(self.n_dst, 1))(*self.groups)
+        h = C.c_void_p()
+        st = lib().mr_nearest_plan_create(grid.handle, C.byref(self._p), _cell_array(sources), self.n,
+                                          _cell_array(dests), self.n_dst, garr, self.n_groups, C.byref(h))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        self.handle = h
+
+    def records(self):
+        """(n_src, n_groups, 5) uint32 array: legs, money, time, via, dst of source i x group g."""
+        import numpy as np
+        out = np.empty((self.n, self.n_groups, 8), dtype=np.uint32)
+        st = lib().mr_nearest_records(self.handle, out.ctypes.data, self.n * self.n_groups)
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return np.ascontiguousarray(out[:, :, :5])
+
+    def device_records(self):
+        """(device pointer, bytes) of the rows: [plan source][record_pitch()] records of 32 B."""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        st = lib().mr_nearest_device_records(self.handle, C.byref(ptr), C.byref(n))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return ptr.value, n.value
+
+    def record_pitch(self) -> int:
+        """Records per row of device_records() (n_groups rounded up to a multiple of 4)."""
+        p = C.c_uint32()
+        st = lib().mr_nearest_record_pitch(self.handle, C.byref(p))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return p.value
+
+    def source_rows(self) -> List[int]:
+        """The device row of each of the caller's sources (repeated sources share a row)."""
+        out = (C.c_uint32 * max(1, self.n))()
+        st = lib().mr_nearest_source_rows(self.handle, out, self.n)
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return list(out)[:self.n]
+
+    def label(self, i: int, g: int) -> Optional[TotalCost]:
+        """The winner's full label, or None for an empty group."""
+        res = mr_result()
+        cap = 64
+        while True:
+            cmds = (mr_command * cap)()
+            st = lib().mr_nearest_label(self.handle, i, g, C.byref(res), cmds, cap)
+            if st == MR_ERR_CAPACITY and res.n_commands > cap:
+                cap = res.n_commands
+                continue
+            break
+        if st == MR_NOT_FOUND:
+            return None
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        res.command_offset = 0
+        return result_from_c(res, cmds)
+
+    def fetch(self):
+        raise NotImplementedError("nearest plans: use records() / label()")
