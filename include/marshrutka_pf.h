@@ -495,21 +495,38 @@ int mr_matrix_label(mr_plan *plan, uint32_t i, uint32_t j, mr_result *out, mr_co
  * plan sources x pitch x 32 B does not fit the device block cache's largest block (16 GiB);
  * MR_ERR_NO_DEVICE as for the other plans.  The mr_matrix_*, mr_sssp_* and pair-plan
  * accessors return MR_ERR_INVALID_ARG on a nearest plan, the mr_nearest_* accessors on any
- * other plan.  MR_ERR_LIMIT for labels holds as stated at mr_status. */
+ * other plan.  MR_ERR_LIMIT for labels holds as stated at mr_status.
+ *
+ * k-nearest (mr_nearest_plan_create_ex with k in 1..MR_NEAREST_MAX_K): the k best per source and
+ * group.  Rank r < k of group g is the r-th least j of the group under the same order
+ * (m[q0], m[q1], m[q2], j): rank 0 is the nearest plan's winner word for word, a cell listed
+ * twice takes two ranks (the earlier listing first), the source among its destinations takes
+ * rank 0, and a rank at or past the group's size is the empty record (dst = 0xFFFFFFFF, all
+ * other words 0); k may exceed every group's size.  A row is n_groups x k records, record
+ * (g, r) at g * k + r.  mr_nearest_plan_create is this call with k = 1, and a plan with k = 1
+ * created either way is the same plan to the byte.  Further errors: MR_ERR_INVALID_ARG for
+ * k = 0 or k > MR_NEAREST_MAX_K (checked with the other arguments, before any device is
+ * touched; mr_last_error names k), MR_ERR_LIMIT when n_groups x k does not fit 32 bits. */
+#define MR_NEAREST_MAX_K 64u /* one list entry per lane of a wave */
 typedef struct mr_nearest_record {
     uint32_t legs, money, time_s;
     uint32_t via;         /* mr_label_record's meaning */
-    uint32_t dst;         /* position j in the caller's list; 0xFFFFFFFF = empty group (all other words 0) */
+    uint32_t dst;         /* position j in the caller's list; 0xFFFFFFFF = empty group or rank (all other words 0) */
     uint32_t reserved[3]; /* 0 */
 } mr_nearest_record;      /* 32 B: four records a 128 B line */
 int mr_nearest_plan_create(const mr_grid *grid, const mr_params *params, const mr_cell_index *sources, uint32_t n_src,
                            const mr_cell_index *dests, uint32_t n_dst, const uint32_t *group_of_dst, uint32_t n_groups,
                            mr_plan **out);
-/* the record of the caller's source i and group g at out[i * n_groups + g] (waits);
- * MR_ERR_CAPACITY if cap_records < n_src * n_groups */
+int mr_nearest_plan_create_ex(const mr_grid *grid, const mr_params *params, const mr_cell_index *sources, uint32_t n_src,
+                              const mr_cell_index *dests, uint32_t n_dst, const uint32_t *group_of_dst, uint32_t n_groups,
+                              uint32_t k, mr_plan **out);
+/* the plan's k (1 for mr_nearest_plan_create); MR_ERR_INVALID_ARG on any other plan */
+int mr_nearest_k(const mr_plan *plan, uint32_t *k);
+/* the record of the caller's source i, group g and rank r at out[(i * n_groups + g) * k + r]
+ * (waits); MR_ERR_CAPACITY if cap_records < n_src * n_groups * k */
 int mr_nearest_records(mr_plan *plan, mr_nearest_record *out, uint64_t cap_records);
-/* device rows: [plan source][pitch] mr_nearest_record, pitch = n_groups rounded up to 4
- * records (whole 128 B lines; pad records are zeros).  Waits for the passes enqueued so far;
+/* device rows: [plan source][pitch] mr_nearest_record, record (g, r) at g * k + r, pitch =
+ * n_groups * k rounded up to 4 records (whole 128 B lines; pad records are zeros).  Waits for the passes enqueued so far;
  * the next mr_plan_run rewrites the rows */
 int mr_nearest_device_records(mr_plan *plan, void **d_records, uint64_t *bytes);
 int mr_nearest_record_pitch(mr_plan *plan, uint32_t *records_per_row);
@@ -518,6 +535,9 @@ int mr_nearest_source_rows(const mr_plan *plan, uint32_t *row_of_source, uint32_
 /* the winner's label, FindPath::eval(sources[i], dests[record.dst]), rebuilt in full:
  * MR_OK, MR_NOT_FOUND for an empty group, MR_ERR_CAPACITY (out->n_commands > cap) or an error */
 int mr_nearest_label(mr_plan *plan, uint32_t i, uint32_t g, mr_result *out, mr_command *cmds, uint32_t cap);
+/* the same for rank r (mr_nearest_label is rank 0): MR_NOT_FOUND for an empty rank,
+ * MR_ERR_INVALID_ARG for r >= k or a plan that is not a nearest plan */
+int mr_nearest_label_ex(mr_plan *plan, uint32_t i, uint32_t g, uint32_t r, mr_result *out, mr_command *cmds, uint32_t cap);
 /* The grid's cells with point of interest `poi` (MR_POI_*; MR_POI_NONE: the cells without
  * one) in row-major order: *n = their number, the first min(cap, *n) written to out (out may
  * be NULL when cap is 0).  MR_ERR_CAPACITY if *n > cap (*n stays set);

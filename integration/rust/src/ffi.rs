@@ -156,6 +156,9 @@ pub struct mr_nearest_record {
     pub reserved: [u32; 3],
 }
 
+/// The largest `k` of `mr_nearest_plan_create_ex` (one list entry per lane of a wave).
+pub const MR_NEAREST_MAX_K: u32 = 64;
+
 /// Opaque handles.
 pub enum mr_grid {}
 pub enum mr_plan {}
@@ -252,6 +255,13 @@ extern "C" {
     pub fn mr_nearest_source_rows(plan: *const mr_plan, row_of_source: *mut u32, n_src: u32) -> c_int;
     pub fn mr_nearest_label(plan: *mut mr_plan, i: u32, g: u32, out: *mut mr_result, cmds: *mut mr_command,
                             cap: u32) -> c_int;
+    // k-nearest: the k best per source and group, record (g, r) at g * k + r of a row
+    pub fn mr_nearest_plan_create_ex(grid: *const mr_grid, params: *const mr_params, sources: *const mr_cell_index,
+                                     n_src: u32, dests: *const mr_cell_index, n_dst: u32, group_of_dst: *const u32,
+                                     n_groups: u32, k: u32, out: *mut *mut mr_plan) -> c_int;
+    pub fn mr_nearest_k(plan: *const mr_plan, k: *mut u32) -> c_int;
+    pub fn mr_nearest_label_ex(plan: *mut mr_plan, i: u32, g: u32, r: u32, out: *mut mr_result, cmds: *mut mr_command,
+                               cap: u32) -> c_int;
     pub fn mr_grid_poi_cells(grid: *const mr_grid, poi: u32, out: *mut mr_cell_index, cap: u32, n: *mut u32) -> c_int;
 
     // misc

@@ -88,7 +88,8 @@ class mr_nearest_record(C.Structure):
                 ("dst", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
-NEAREST_NONE = 0xFFFFFFFF  # mr_nearest_record.dst of an empty group
+NEAREST_NONE = 0xFFFFFFFF  # mr_nearest_record.dst of an empty group (k-nearest: or of an empty rank)
+MR_NEAREST_MAX_K = 64      # the largest k of mr_nearest_plan_create_ex
 
 assert C.sizeof(mr_cell_index) == 8
 assert C.sizeof(mr_cell) == 16

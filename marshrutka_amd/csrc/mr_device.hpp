@@ -158,6 +158,95 @@ __device__ __forceinline__ uint32_t bcast(uint32_t x, uint32_t l) {
     return uint32_t(__builtin_amdgcn_readlane(int(x), int(l)));
 }
 
+// ---- k-nearest plans: a wave's sorted list of the k least keys (DESIGN.md section 3b''') ----
+// Lane r < k holds entry r of the current group's list: the key (metrics in comparator order,
+// the sorted index, which is unique, so no two keys are equal) and the record's via.  All ones:
+// no entry.  Lanes at and past k hold what was pushed out of the list; nothing reads them.
+struct KList {
+    uint32_t e0, e1, e2, e3, via;
+};
+__device__ __forceinline__ void klist_clear(KList &l) {
+    l.e0 = l.e1 = l.e2 = l.e3 = 0xFFFFFFFFu;
+    l.via = 0u;
+}
+__device__ __forceinline__ bool key_lt(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3, uint32_t b0, uint32_t b1,
+                                       uint32_t b2, uint32_t b3) {
+    return a0 < b0 || (a0 == b0 && (a1 < b1 || (a1 == b1 && (a2 < b2 || (a2 == b2 && a3 < b3)))));
+}
+// A chunk's candidates into the list (all 64 lanes active): lane l of the `alive` ones offers
+// (n0, n1, n2, cfirst + l) with `via`.  While a candidate lies strictly below entry k - 1 (the
+// threshold, wave-uniform), the least such candidate is narrowed out word by word (four
+// wave_min_u32, the sorted index last), inserted — every lane whose entry is greater takes its
+// lower neighbour's entry, or the new key where the neighbour's is not greater — and struck
+// from the candidates.  Candidates leave in ascending order, so one inserted from this chunk is
+// never pushed out by a later one of it: after k insertions the threshold is below every
+// candidate left, and a chunk costs at most min(k, count) insertions whatever order the
+// destinations arrive in.
+__device__ __forceinline__ void klist_chunk(KList &l, uint32_t k, uint32_t n0, uint32_t n1, uint32_t n2, uint32_t cfirst,
+                                            uint32_t via, bool alive) {
+    const uint32_t lane = lane_id(), c3 = cfirst + lane, kt = k - 1u;
+    bool beats = alive && key_lt(n0, n1, n2, c3, bcast(l.e0, kt), bcast(l.e1, kt), bcast(l.e2, kt), bcast(l.e3, kt));
+    while (__ballot(beats) != 0) {
+        bool c = beats;
+        const uint32_t m0 = wave_min_u32(c ? n0 : 0xFFFFFFFFu);
+        c = c && n0 == m0;
+        const uint32_t m1 = wave_min_u32(c ? n1 : 0xFFFFFFFFu);
+        c = c && n1 == m1;
+        const uint32_t m2 = wave_min_u32(c ? n2 : 0xFFFFFFFFu);
+        c = c && n2 == m2;
+        const uint32_t m3 = wave_min_u32(c ? c3 : 0xFFFFFFFFu);
+        const uint32_t wl = (m3 - cfirst) & 63u;  // the winner's lane
+        const uint32_t mv = bcast(via, wl);
+        const bool gt = key_lt(m0, m1, m2, m3, l.e0, l.e1, l.e2, l.e3);
+        const unsigned long long gm = __ballot(gt);
+        const bool shift = lane > 0u && ((gm >> ((lane - 1u) & 63u)) & 1ull) != 0;  // the lower neighbour's is greater too
+        const uint32_t p0 = uint32_t(__shfl_up(int(l.e0), 1)), p1 = uint32_t(__shfl_up(int(l.e1), 1));
+        const uint32_t p2 = uint32_t(__shfl_up(int(l.e2), 1)), p3 = uint32_t(__shfl_up(int(l.e3), 1));
+        const uint32_t pv = uint32_t(__shfl_up(int(l.via), 1));
+        if (gt) {
+            l.e0 = shift ? p0 : m0;
+            l.e1 = shift ? p1 : m1;
+            l.e2 = shift ? p2 : m2;
+            l.e3 = shift ? p3 : m3;
+            l.via = shift ? pv : mv;
+        }
+        alive = alive && lane != wl;
+        beats = alive && key_lt(n0, n1, n2, c3, bcast(l.e0, kt), bcast(l.e1, kt), bcast(l.e2, kt), bcast(l.e3, kt));
+    }
+}
+// the two 16 B halves of list entry l as the 32 B record (pos: the caller's position, read by
+// the caller from KArgs::nr_pos[l.e3]); no entry: the empty record
+__device__ __forceinline__ void klist_record(const KList &l, uint32_t q0, uint32_t q1, uint32_t pos, uint4 &lo, uint4 &hi) {
+    lo = make_uint4(0u, 0u, 0u, 0u);
+    hi = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+    if (l.e3 != 0xFFFFFFFFu) {
+        // (metric m is key word i where q_i == m)
+        lo = make_uint4(q0 == 0 ? l.e0 : (q1 == 0 ? l.e1 : l.e2), q0 == 1 ? l.e0 : (q1 == 1 ? l.e1 : l.e2),
+                        q0 == 2 ? l.e0 : (q1 == 2 ? l.e1 : l.e2), l.via);
+        hi.x = pos;
+    }
+}
+// The records of groups [cur, upto) of a source's row, upto > cur: the list is group cur's (lane
+// r < k stores record cur * k + r, two 16 B stores; four lanes a 128 B line when k is a multiple
+// of 4), the groups after it are empty.  Leaves the list cleared and cur = upto.
+__device__ __forceinline__ void klist_flush(uint4 *row, const uint32_t *pos, uint32_t k, uint32_t &cur, uint32_t upto,
+                                            KList &l, uint32_t q0, uint32_t q1) {
+    const uint32_t lane = lane_id();
+    if (lane < k) {
+        uint4 lo, hi;
+        klist_record(l, q0, q1, l.e3 != 0xFFFFFFFFu ? pos[l.e3] : 0u, lo, hi);
+        const unsigned long long i = (unsigned long long)cur * k + lane;
+        row[2ull * i] = lo;
+        row[2ull * i + 1] = hi;
+    }
+    klist_clear(l);
+    for (unsigned long long i = (unsigned long long)(cur + 1u) * k + lane; i < (unsigned long long)upto * k; i += 64) {
+        row[2ull * i] = make_uint4(0u, 0u, 0u, 0u);
+        row[2ull * i + 1] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+    }
+    cur = upto;
+}
+
 // A label viewed for comparison: metrics, length, prefix pointer (table
 // index, 0 = empty prefix) and the last <= 2 commands.  Scalar fields only, so
 // nothing is runtime-indexed (no scratch).
@@ -917,6 +1006,10 @@ struct Core {
             a->out_tab[tb + t] = R[t];
             a->out_lex[tb + t] = kNone32;
         }
+        if (a->nr_k > 1u) {
+            write_knearest(s_idx);
+            return;
+        }
         constexpr uint32_t nw = kBS / 64, kW = 8;  // per wave: valid, the key's four words, via, group
         static_assert(nw * kW * 4 <= 64 * 4, "write_nearest: the waves' keys must fit the dst area (lds_layout: 64 words)");
         const uint32_t lane = lane_id(), wv = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
@@ -997,6 +1090,45 @@ struct Core {
             for (uint32_t k = 2u * ng; k < 2u * pitch; ++k) row[k] = make_uint4(0u, 0u, 0u, 0u);
             a->src_state[s_idx] = 2;
         }
+    }
+    // k-nearest plans (DESIGN.md section 3b'''; the table is written by write_nearest): the first
+    // wave walks the chunk table alone, a chunk a step, with knearest_kernel's list routine
+    // (klist_chunk), each candidate the expansion of the cell word write_all would store, and
+    // stores a group's k records when the next group begins.  The search before it costs
+    // milliseconds a source; the caller's barrier holds the other waves until the row is written.
+    __device__ void write_knearest(uint32_t s_idx) const {
+        if (threadIdx.x >= 64u) return;
+        const DevParams &p = P;
+        const uint32_t T = p.NS + 1, lane = lane_id();
+        const uint32_t ng = a->nr_ngroups, nc = a->nr_nchunk, pitch = a->mx_pitch;
+        const uint32_t k = uint32_t(__builtin_amdgcn_readfirstlane(int(a->nr_k)));
+        uint4 *row = a->mx_rows + 2ull * (unsigned long long)s_idx * pitch;
+        const FfRatio ff{p.ff_num, p.ff_den};
+        const uint32_t q0 = p.perm[0], q1 = p.perm[1], q2 = p.perm[2];
+        uint32_t cur = 0;
+        KList l;
+        klist_clear(l);
+        for (uint32_t c = 0; c < nc; ++c) {
+            const uint4 ch = a->nr_chunk[c];
+            const uint32_t cg = uint32_t(__builtin_amdgcn_readfirstlane(int(ch.x)));
+            const uint32_t cfirst = uint32_t(__builtin_amdgcn_readfirstlane(int(ch.y)));
+            const bool cand = lane < ch.z;
+            if (cg != cur) klist_flush(row, a->nr_pos, k, cur, cg, l, q0, q1);
+            mr_label_record o{0u, 0u, 0u, 0u};
+            if (cand) {
+                const uint32_t xy = a->mx_dst[cfirst + lane].x;
+                const int x = int(short(xy & 0xFFFFu)), y = int(short(xy >> 16));
+                const uint32_t v = uint32_t(y + int(p.H)) * p.S + uint32_t(x + int(p.H));
+                if (!expand_word(cell_word(v), T, ff, [&](uint32_t t, uint32_t q) { return R[t].m[q]; }, o))
+                    flag(kErrChain);
+            }
+            const auto om = [&](uint32_t q) { return q == 0 ? o.legs : (q == 1 ? o.money : o.time_s); };
+            klist_chunk(l, k, om(q0), om(q1), om(q2), cfirst, o.via, cand);
+        }
+        if (cur < ng) klist_flush(row, a->nr_pos, k, cur, ng, l, q0, q1);
+        // pad records of the row: zeros (fewer than 4 records)
+        if (lane < 2u * (pitch - ng * k)) row[2ull * ng * k + lane] = make_uint4(0u, 0u, 0u, 0u);
+        if (lane == 0) a->src_state[s_idx] = 2;
     }
     // all-destinations mode: the label table and a cell word for every cell (CellWord:
     // the settled state word's walk (b, k) as it stands)

@@ -256,12 +256,15 @@ struct KArgs {
     // nr_pos[k] the caller's position of sorted destination k.  nr_chunk[c] = {group, first
     // sorted destination, count <= 64, 0}: the chunks in sorted order, none spans two groups;
     // nr_gstart[g] = the first chunk of group g (nr_ngroups + 1 entries, the last = nr_nchunk).
-    // mx_pitch = nr_ngroups rounded up to 4 records (a 128 B line)
+    // mx_pitch = nr_ngroups rounded up to 4 records (a 128 B line).
+    // k-nearest plans (nr_k > 1, DESIGN.md section 3b'''): record g * nr_k + r the r-th best
+    // destination of group g, mx_pitch = nr_ngroups * nr_k rounded up to 4 records
     const uint32_t *nr_pos;
     const uint4 *nr_chunk;
     const uint32_t *nr_gstart;
     uint32_t nr_ngroups;
     uint32_t nr_nchunk;
+    uint32_t nr_k;
 };
 // KArgs::all_mode: a cell word per (source, cell), a record per (source, listed destination),
 // or a record per (source, group of listed destinations)

@@ -41,6 +41,8 @@ hipError_t launch_matrix(const KArgs *d_args, const uint32_t perm[3], uint32_t g
 int matrix_blocks_per_cu(const uint32_t perm[3]);
 hipError_t launch_nearest(const KArgs *d_args, const uint32_t perm[3], uint32_t gx, hipStream_t stream);
 int nearest_blocks_per_cu(const uint32_t perm[3]);
+hipError_t launch_knearest(const KArgs *d_args, const uint32_t perm[3], uint32_t gx, hipStream_t stream);
+int knearest_blocks_per_cu(const uint32_t perm[3]);
 hipError_t launch_hub_fill(const KArgs *hub_args, const KArgs *fill_args, const uint32_t perm[3], uint32_t spw,
                            uint32_t hub_blocks, uint32_t fill_blocks, uint32_t lds_bytes, hipStream_t stream);
 int hub_fill_blocks_per_cu(const uint32_t perm[3], uint32_t spw, uint32_t lds_bytes);
@@ -1674,12 +1676,13 @@ struct mr_plan {
     // nearest plans: mx.dst holds the destinations stable-sorted by group (mx.dst_v stays in
     // the caller's order), mx.rows two uint4 a record, mx.pitch = n_groups rounded up to 4;
     // the caller's groups, the sorted destinations' caller positions, the chunk table and the
-    // groups' first chunks (KArgs::nr_*)
+    // groups' first chunks (KArgs::nr_*).  k > 1: a k-nearest plan, n_groups * k records a row
+    // (record g * k + r the r-th best of group g), mx.pitch = n_groups * k rounded up to 4
     struct Nearest {
         std::vector<uint32_t> group;
         DevBuf<uint32_t> pos, gstart;
         DevBuf<uint4> chunk;
-        uint32_t n_groups = 0;
+        uint32_t n_groups = 0, k = 1;
     } nr;
     struct Hub {
         uint32_t n_lane = 0;               // sources on the lane kernel; the rest on hub_kernel
@@ -2517,7 +2520,7 @@ static int plan_matrix_outputs(mr_plan *pl) {
 // group (so the smallest sorted index of a group is the caller's smallest position), their
 // caller positions, the chunk table {group, first sorted destination, count <= 64} whose
 // chunks never span two groups, the groups' first chunks, and the record rows,
-// [plan source][pitch] of 32 B, pitch = n_groups rounded up to whole 128 B lines
+// [plan source][pitch] of 32 B, pitch = n_groups x k rounded up to whole 128 B lines
 static int plan_nearest_outputs(mr_plan *pl) {
     const HostPlan &hp = pl->hp;
     KArgs &ka = pl->ka;
@@ -2526,7 +2529,7 @@ static int plan_nearest_outputs(mr_plan *pl) {
     const mr_grid *g = pl->grid;
     m.n_dst = uint32_t(m.dst_v.size());
     const uint32_t ng = nr.n_groups;
-    const uint64_t pitch = (uint64_t(ng) + 3) / 4 * 4, ns = std::max<uint32_t>(ka.nsrc, 1);
+    const uint64_t pitch = (uint64_t(ng) * nr.k + 3) / 4 * 4, ns = std::max<uint32_t>(ka.nsrc, 1);
     if (pitch > 0xFFFFFFFFull || ns * pitch > kMatrixMaxBytes / sizeof(mr_nearest_record))
         return fail(MR_ERR_LIMIT, "nearest plan: " + std::to_string(ns) + " sources x " + std::to_string(pitch) +
                                       " records of 32 B exceed the device block cache's largest block");
@@ -2568,7 +2571,8 @@ static int plan_nearest_outputs(mr_plan *pl) {
     ka.nr_gstart = nr.gstart.get();
     ka.nr_ngroups = ng;
     ka.nr_nchunk = uint32_t(chunk.size());
-    m.per_cu = uint32_t(std::max(1, nearest_blocks_per_cu(hp.p.perm)));
+    ka.nr_k = nr.k;
+    m.per_cu = uint32_t(std::max(1, nr.k > 1 ? knearest_blocks_per_cu(hp.p.perm) : nearest_blocks_per_cu(hp.p.perm)));
     return MR_OK;
 }
 
@@ -2849,7 +2853,7 @@ static int plan_overlap(mr_plan *pl) {
 
 static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *qs, uint32_t n, uint32_t max_cmds,
                        mr_plan **out, bool all_mode = false, std::vector<uint32_t> *matrix_dst = nullptr,
-                       std::vector<uint32_t> *nearest_group = nullptr, uint32_t n_groups = 0) {
+                       std::vector<uint32_t> *nearest_group = nullptr, uint32_t n_groups = 0, uint32_t nearest_k = 1) {
     if (!out || (n && !qs)) return fail(MR_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     if (!mr_device_available()) return fail(MR_ERR_NO_DEVICE, "no gfx950 device visible (no CPU fallback)");
@@ -2866,6 +2870,7 @@ static int plan_create(const mr_grid *g, const mr_params *prm, const mr_query *q
     if (pl->nearest) {
         pl->nr.group = std::move(*nearest_group);
         pl->nr.n_groups = n_groups;
+        pl->nr.k = nearest_k;
     }
     HostPlan &hp = pl->hp;
     int st = build_plan(g, prm, qs, n, max_cmds, hp, !all_mode);
@@ -3005,7 +3010,8 @@ static hipError_t run_all(mr_plan *pl, hipStream_t s) {
     Event f0;
     if (e == hipSuccess) f0 = fill_start(s);
     if (e == hipSuccess)
-        e = pl->nearest  ? launch_nearest(k.args_fill.get(), pl->ka.p.perm, gx, s)
+        e = pl->nearest  ? (pl->nr.k > 1 ? launch_knearest(k.args_fill.get(), pl->ka.p.perm, gx, s)
+                                         : launch_nearest(k.args_fill.get(), pl->ka.p.perm, gx, s))
             : pl->matrix ? launch_matrix(k.args_fill.get(), pl->ka.p.perm, gx, s)
                          : launch_fill(k.args_fill.get(), pl->ka.p.perm, gx, 1, s);
     // the slot's tables are free again once this fill has read them
@@ -4438,20 +4444,25 @@ extern "C" int mr_matrix_label(mr_plan *pl, uint32_t i, uint32_t j, mr_result *r
 }
 
 // ------------------------------------------------------------ nearest of a set
-extern "C" int mr_nearest_plan_create(const mr_grid *g, const mr_params *prm, const mr_cell_index *sources, uint32_t n_src,
-                                      const mr_cell_index *dests, uint32_t n_dst, const uint32_t *group_of_dst,
-                                      uint32_t n_groups, mr_plan **out) {
+extern "C" int mr_nearest_plan_create_ex(const mr_grid *g, const mr_params *prm, const mr_cell_index *sources, uint32_t n_src,
+                                         const mr_cell_index *dests, uint32_t n_dst, const uint32_t *group_of_dst,
+                                         uint32_t n_groups, uint32_t k, mr_plan **out) {
     if (!g || !prm || !out || !sources || !dests) return fail(MR_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     if (!n_src || !n_dst || !n_groups)
         return fail(MR_ERR_INVALID_ARG, "a nearest plan needs at least one source, one destination and one group");
     if (n_groups > n_dst) return fail(MR_ERR_INVALID_ARG, "a nearest plan cannot have more groups than destinations");
+    if (k == 0 || k > MR_NEAREST_MAX_K)
+        return fail(MR_ERR_INVALID_ARG, "a nearest plan's k = " + std::to_string(k) + " is not in 1.." + std::to_string(MR_NEAREST_MAX_K));
     std::vector<uint32_t> grp(n_dst, 0u);
     for (uint32_t j = 0; group_of_dst && j < n_dst; ++j) {
         if (group_of_dst[j] >= n_groups)
             return fail(MR_ERR_INVALID_ARG, "group of destination " + std::to_string(j) + " is not below n_groups");
         grp[j] = group_of_dst[j];
     }
+    if (uint64_t(n_groups) * k > 0xFFFFFFFFull)
+        return fail(MR_ERR_LIMIT, "nearest plan: " + std::to_string(n_groups) + " groups x k = " + std::to_string(k) +
+                                      " records a row do not fit 32 bits");
     if (!mr_device_available()) return fail(MR_ERR_NO_DEVICE, "no gfx950 device visible (no CPU fallback)");
     std::vector<uint32_t> dv(n_dst);
     for (uint32_t i = 0; i < n_src; ++i) {
@@ -4463,9 +4474,22 @@ extern "C" int mr_nearest_plan_create(const mr_grid *g, const mr_params *prm, co
             return fail(MR_ERR_INVALID_INDEX, "destination " + std::to_string(j) + " is not a grid cell");
     std::vector<mr_query> qs(n_src);
     for (uint32_t i = 0; i < n_src; ++i) qs[i].from = qs[i].to = sources[i];
-    const int st = plan_create(g, prm, qs.data(), n_src, 16, out, true, &dv, &grp, n_groups);
+    const int st = plan_create(g, prm, qs.data(), n_src, 16, out, true, &dv, &grp, n_groups, k);
     if (st == MR_OK) (*out)->mx.n_src = n_src;
     return st;
+}
+
+extern "C" int mr_nearest_plan_create(const mr_grid *g, const mr_params *prm, const mr_cell_index *sources, uint32_t n_src,
+                                      const mr_cell_index *dests, uint32_t n_dst, const uint32_t *group_of_dst,
+                                      uint32_t n_groups, mr_plan **out) {
+    return mr_nearest_plan_create_ex(g, prm, sources, n_src, dests, n_dst, group_of_dst, n_groups, 1u, out);
+}
+
+extern "C" int mr_nearest_k(const mr_plan *pl, uint32_t *k) {
+    if (!pl || !pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a nearest plan");
+    if (!k) return fail(MR_ERR_INVALID_ARG, "null output");
+    *k = pl->nr.k;
+    return MR_OK;
 }
 
 // a nearest plan whose last pass raised no device error (waits for the plan)
@@ -4479,9 +4503,9 @@ extern "C" int mr_nearest_records(mr_plan *pl, mr_nearest_record *out, uint64_t 
     if (int st = nearest_plan(pl)) return st;
     if (!out) return fail(MR_ERR_INVALID_ARG, "null output");
     const mr_plan::Matrix &m = pl->mx;
-    const uint32_t ng = pl->nr.n_groups;
+    const uint32_t ng = pl->nr.n_groups * pl->nr.k;  // records a source
     if (cap_records < uint64_t(m.n_src) * ng)
-        return fail(MR_ERR_CAPACITY, "mr_nearest_records: output shorter than n_src x n_groups");
+        return fail(MR_ERR_CAPACITY, "mr_nearest_records: output shorter than n_src x n_groups x k");
     // as mr_matrix_records: one copy when the rows are the caller's table, else a row at a time
     const mr_nearest_record *rows = reinterpret_cast<const mr_nearest_record *>(m.rows.get());
     bool in_order = m.pitch == ng;
@@ -4521,17 +4545,23 @@ extern "C" int mr_nearest_source_rows(const mr_plan *pl, uint32_t *row_of_source
 }
 
 extern "C" int mr_nearest_label(mr_plan *pl, uint32_t i, uint32_t g, mr_result *res, mr_command *cmds, uint32_t cap) {
+    return mr_nearest_label_ex(pl, i, g, 0u, res, cmds, cap);
+}
+
+extern "C" int mr_nearest_label_ex(mr_plan *pl, uint32_t i, uint32_t g, uint32_t r, mr_result *res, mr_command *cmds,
+                                   uint32_t cap) {
     if (int st = nearest_plan(pl)) return st;
     if (!res) return fail(MR_ERR_INVALID_ARG, "null result");
     const mr_plan::Matrix &m = pl->mx;
     if (i >= m.n_src || g >= pl->nr.n_groups) return fail(MR_ERR_INVALID_ARG, "nearest index");
+    if (r >= pl->nr.k) return fail(MR_ERR_INVALID_ARG, "nearest rank " + std::to_string(r) + " is not below k = " + std::to_string(pl->nr.k));
     const uint32_t si = pl->src_of_input[i];
     mr_nearest_record win;
-    if (hipMemcpy(&win, reinterpret_cast<const mr_nearest_record *>(m.rows.get()) + size_t(si) * m.pitch + g, sizeof(win),
-                  hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(&win, reinterpret_cast<const mr_nearest_record *>(m.rows.get()) + size_t(si) * m.pitch + size_t(g) * pl->nr.k + r,
+                  sizeof(win), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(MR_ERR_DEVICE, "copy label");
     std::memset(res, 0, sizeof(*res));
-    if (win.dst == kNone32) {  // an empty group
+    if (win.dst == kNone32) {  // an empty group, or a rank at or past the group's size
         res->status = MR_NOT_FOUND;
         return MR_NOT_FOUND;
     }

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "mr_matrix_source_rows", "mr_matrix_label",
     "mr_nearest_plan_create", "mr_nearest_records", "mr_nearest_device_records", "mr_nearest_record_pitch",
     "mr_nearest_source_rows", "mr_nearest_label", "mr_grid_poi_cells",
+    "mr_nearest_plan_create_ex", "mr_nearest_k", "mr_nearest_label_ex",
 ]
 
 
@@ -181,6 +182,15 @@ def lib():
         L.mr_nearest_label.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(mr_result), C.POINTER(mr_command),
                                        C.c_uint32]
         L.mr_nearest_label.restype = C.c_int
+        L.mr_nearest_plan_create_ex.argtypes = [vp, C.POINTER(mr_params), C.POINTER(mr_cell_index), C.c_uint32,
+                                                C.POINTER(mr_cell_index), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
+                                                C.c_uint32, C.POINTER(vp)]
+        L.mr_nearest_plan_create_ex.restype = C.c_int
+        L.mr_nearest_k.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.mr_nearest_k.restype = C.c_int
+        L.mr_nearest_label_ex.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mr_result),
+                                          C.POINTER(mr_command), C.c_uint32]
+        L.mr_nearest_label_ex.restype = C.c_int
         L.mr_grid_poi_cells.argtypes = [vp, C.c_uint32, C.POINTER(mr_cell_index), C.c_uint32, C.POINTER(C.c_uint32)]
         L.mr_grid_poi_cells.restype = C.c_int
         _lib = L
@@ -357,18 +367,21 @@ class FindPath:
         plan.run()
         return plan.records()
 
-    def eval_nearest(self, sources: Sequence[CellIndex], dests: Sequence[CellIndex], groups: Optional[Sequence[int]] = None):
+    def eval_nearest(self, sources: Sequence[CellIndex], dests: Sequence[CellIndex], groups: Optional[Sequence[int]] = None,
+                     k: Optional[int] = None):
         """The best destination of each group for every source after one pass of a NearestPlan:
         a (n_src, n_groups, 5) uint32 array of legs, money, time, via, dst (the winner's position
-        in `dests`; 0xFFFFFFFF and zeros for an empty group)."""
-        plan = NearestPlan(self.grid, self.params(), sources, dests, groups)
+        in `dests`; 0xFFFFFFFF and zeros for an empty group).  With k: the k best in order, a
+        (n_src, n_groups, k, 5) array (ranks at or past a group's size are empty records)."""
+        plan = NearestPlan(self.grid, self.params(), sources, dests, groups, k=k)
         plan.run()
         return plan.records()
 
-    def eval_nearest_poi(self, sources: Sequence[CellIndex], pois: Sequence[int] = (abi.POI_FOUNTAIN, abi.POI_FORUM)):
+    def eval_nearest_poi(self, sources: Sequence[CellIndex], pois: Sequence[int] = (abi.POI_FOUNTAIN, abi.POI_FORUM),
+                         k: Optional[int] = None):
         """The nearest cell of each point-of-interest kind for every source, one group a kind:
         (records as eval_nearest gives them, the destination list the records' dst indexes).
-        A kind the map lacks is an empty group."""
+        A kind the map lacks is an empty group.  With k: the k nearest of each kind."""
         import numpy as np
         dests: List[CellIndex] = []
         groups: List[int] = []
@@ -379,10 +392,10 @@ class FindPath:
                 dests += cells
                 groups += [len(present)] * len(cells)
                 present.append(g)
-        out = np.zeros((len(sources), len(pois), 5), dtype=np.uint32)
-        out[:, :, 4] = abi.NEAREST_NONE
+        out = np.zeros((len(sources), len(pois), 5) if k is None else (len(sources), len(pois), k, 5), dtype=np.uint32)
+        out[..., 4] = abi.NEAREST_NONE
         if dests:
-            plan = NearestPlan(self.grid, self.params(), sources, dests, groups, n_groups=len(present))
+            plan = NearestPlan(self.grid, self.params(), sources, dests, groups, n_groups=len(present), k=k)
             plan.run()
             out[:, present] = plan.records()
         return out, dests
@@ -848,10 +861,12 @@ class MatrixPlan(Plan):
 class NearestPlan(Plan):
     """Nearest of a set: run() keeps, for every source and destination group, the 32 B record of
     the group's best destination (the least metrics in the parameters' order, ties to the smallest
-    position in `dests`) and which destination it was; label(i, g) rebuilds its full TotalCost."""
+    position in `dests`) and which destination it was; label(i, g) rebuilds its full TotalCost.
+    With k in 1..MR_NEAREST_MAX_K: the k best of every group in that order (mr_nearest_plan_create_ex),
+    records() is (n_src, n_groups, k, 5) and label(i, g, r) the label of rank r."""
 
     def __init__(self, grid: MapGrid, params: Params, sources: Sequence[CellIndex], dests: Sequence[CellIndex],
-                 groups: Optional[Sequence[int]] = None, n_groups: Optional[int] = None):
+                 groups: Optional[Sequence[int]] = None, n_groups: Optional[int] = None, k: Optional[int] = None):
         self.grid = grid
         self.n = len(sources)
         self.n_dst = len(dests)
@@ -869,21 +884,40 @@ class NearestPlan(Plan):
             if any(g < 0 or g > 0xFFFFFFFF for g in self.groups):
                 raise EngineError(abi.MR_ERR_INVALID_ARG, "groups: ids are unsigned 32-bit")
             garr = (C.c_uint32 * max(self.n_dst, 1))(*self.groups)
+        self._k = k
+        if k is not None and not 0 <= int(k) <= 0xFFFFFFFF:
+            raise EngineError(abi.MR_ERR_INVALID_ARG, "k: an unsigned 32-bit count")
         h = C.c_void_p()
-        st = lib().mr_nearest_plan_create(grid.handle, C.byref(self._p), _cell_array(sources), self.n,
-                                          _cell_array(dests), self.n_dst, garr, self.n_groups, C.byref(h))
+        if k is None:
+            st = lib().mr_nearest_plan_create(grid.handle, C.byref(self._p), _cell_array(sources), self.n,
+                                              _cell_array(dests), self.n_dst, garr, self.n_groups, C.byref(h))
+        else:
+            st = lib().mr_nearest_plan_create_ex(grid.handle, C.byref(self._p), _cell_array(sources), self.n,
+                                                 _cell_array(dests), self.n_dst, garr, self.n_groups, int(k), C.byref(h))
         if st != MR_OK:
             raise EngineError(st, last_error())
         self.handle = h
 
-    def records(self):
-        """(n_src, n_groups, 5) uint32 array: legs, money, time, via, dst of source i x group g."""
-        import numpy as np
-        out = np.empty((self.n, self.n_groups, 8), dtype=np.uint32)
-        st = lib().mr_nearest_records(self.handle, out.ctypes.data, self.n * self.n_groups)
+    @property
+    def k(self) -> int:
+        """The records kept per source and group (mr_nearest_k): 1 for a plan made without k."""
+        out = C.c_uint32()
+        st = lib().mr_nearest_k(self.handle, C.byref(out))
         if st != MR_OK:
             raise EngineError(st, last_error())
-        return np.ascontiguousarray(out[:, :, :5])
+        return out.value
+
+    def records(self):
+        """(n_src, n_groups, 5) uint32 array: legs, money, time, via, dst of source i x group g;
+        a plan made with k: (n_src, n_groups, k, 5), rank r of the group at [i, g, r]."""
+        import numpy as np
+        k = 1 if self._k is None else int(self._k)
+        out = np.empty((self.n, self.n_groups * k, 8), dtype=np.uint32)
+        st = lib().mr_nearest_records(self.handle, out.ctypes.data, self.n * self.n_groups * k)
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        rec = np.ascontiguousarray(out[:, :, :5])
+        return rec if self._k is None else rec.reshape(self.n, self.n_groups, k, 5)
 
     def device_records(self):
         """(device pointer, bytes) of the rows: [plan source][record_pitch()] records of 32 B."""
@@ -894,7 +928,7 @@ class NearestPlan(Plan):
         return ptr.value, n.value
 
     def record_pitch(self) -> int:
-        """Records per row of device_records() (n_groups rounded up to a multiple of 4)."""
+        """Records per row of device_records() (n_groups x k rounded up to a multiple of 4)."""
         p = C.c_uint32()
         st = lib().mr_nearest_record_pitch(self.handle, C.byref(p))
         if st != MR_OK:
@@ -909,13 +943,13 @@ class NearestPlan(Plan):
             raise EngineError(st, last_error())
         return list(out)[:self.n]
 
-    def label(self, i: int, g: int) -> Optional[TotalCost]:
-        """The winner's full label, or None for an empty group."""
+    def label(self, i: int, g: int, r: int = 0) -> Optional[TotalCost]:
+        """The full label of the group's rank r (0: the winner), or None for an empty group or rank."""
         res = mr_result()
         cap = 64
         while True:
             cmds = (mr_command * cap)()
-            st = lib().mr_nearest_label(self.handle, i, g, C.byref(res), cmds, cap)
+            st = lib().mr_nearest_label_ex(self.handle, i, g, r, C.byref(res), cmds, cap)
             if st == MR_ERR_CAPACITY and res.n_commands > cap:
                 cap = res.n_commands
                 continue
