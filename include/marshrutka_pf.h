@@ -245,8 +245,10 @@ int mr_plan_fetch(mr_plan *plan, mr_result *results, mr_command *pool, uint64_t 
  * A label longer than max_cmds keeps {0xFFFFFFFF, offset, count} in its first
  * slot and its commands in the plan's own overflow pool.  The command slots at or past
  * a record's n_commands (past the first slot of a longer label) are unspecified: a
- * kernel that stores whole rows (the lane memo's staged read-off, plans of max_cmds <= 4)
- * writes them as zeros, the others leave them as they were.  The fourth (`pad`) word of
+ * kernel that stores whole rows (the lane memo's staged read-off and its record-per-lane
+ * read-off, plans of max_cmds <= 4) writes them as zeros, the others leave them as they
+ * were; the command slots of a record whose status is MR_ERR_CAPACITY are not written.
+ * The fourth (`pad`) word of
  * every written slot is zero.  The call waits for the
  * passes enqueued so far, so the words behind the pointers are whole when it
  * returns; a later mr_plan_run rewrites them (order a reader on another stream with

@@ -314,12 +314,66 @@ __device__ __forceinline__ void gstore16(void *p, uint32_t x, uint32_t y, uint32
 }
 __device__ __forceinline__ uint32_t gload32(const uint32_t *p) { return *(const __attribute__((address_space(1))) uint32_t *)p; }
 __device__ __forceinline__ uint32_t gload8(const uint8_t *p) { return *(const __attribute__((address_space(1))) uint8_t *)p; }
+// (kLaneQuery) two words from global memory, and from LDS, by address
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint2 gload64(const uint2 *p) {
+    const u32x2 v = *(const __attribute__((address_space(1))) u32x2 *)p;
+    return make_uint2(v.x, v.y);
+}
+__device__ __forceinline__ uint2 lload64(const uint2 *p) {
+    const u32x2 v = *(const __attribute__((address_space(3))) u32x2 *)p;
+    return make_uint2(v.x, v.y);
+}
+// (kLaneQuery) the counters' atomics by address: a generic atomic whose result is not
+// waited for stays pending on both memory counters, and every wait after it is one for zero
+__device__ __forceinline__ void gatomic_or(uint32_t *p, uint32_t v) {
+    (void)__hip_atomic_fetch_or((__attribute__((address_space(1))) uint32_t *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t gatomic_add(uint32_t *p, uint32_t v) {
+    return __hip_atomic_fetch_add((__attribute__((address_space(1))) uint32_t *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// (kLaneQuery) everything this wave has in flight, waited for.  It ends the rare paths of
+// the chunk loop that store or load a varying number of times: behind it nothing is
+// pending, so where such a path joins the ordinary one the compiler's wait counts are the
+// ordinary path's (s_waitcnt vmcnt(0) lgkmcnt(0); gfx9 encoding, expcnt left at 7)
+__device__ __forceinline__ void lane_drain() { __builtin_amdgcn_s_waitcnt(0x0070); }
+// kLaneQuery: the command slots of a record that are assembled in registers and stored as
+// one fixed sequence (plans of up to this many slots; wider ones keep the stores inside
+// the label's walk)
+constexpr uint32_t kLaneRowSlots = 4;
+// (kLaneQuery) lane i of a quad holds x[0 .. 3]; afterwards its x[j] is what lane j of the
+// quad held in x[i] (a 4 x 4 transpose over lanes and registers: the lanes whose index
+// differs in bit b exchange the registers whose index differs in bit b, b = 0, 1).  Every
+// lane of the wave must be active.
+__device__ __forceinline__ void quad_transpose(uint32_t (&x)[4]) {
+    const bool o1 = lane_id() & 1u, o2 = lane_id() & 2u;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j += 2u) {
+        const uint32_t send = o1 ? x[j] : x[j + 1u];
+        const uint32_t recv = uint32_t(__builtin_amdgcn_update_dpp(0, int(send), 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
+        x[j] = o1 ? recv : x[j];
+        x[j + 1u] = o1 ? x[j + 1u] : recv;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 2u; ++j) {
+        const uint32_t send = o2 ? x[j] : x[j + 2u];
+        const uint32_t recv = uint32_t(__builtin_amdgcn_update_dpp(0, int(send), 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
+        x[j] = o2 ? recv : x[j];
+        x[j + 2u] = o2 ? x[j + 2u] : recv;
+    }
+}
+// (kLaneQuery) 16 bytes through a buffer descriptor at a byte offset; kLaneDrop: an offset
+// past the end of every buffer emit_q describes, for a lane that stores nothing
+constexpr uint32_t kLaneDrop = 0x40000000u;
+__device__ __forceinline__ void bstore16(__amdgpu_buffer_rsrc_t r, uint32_t off, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{x, y, z, w}, r, int(off), 0, 0);
+}
 
 template <uint32_t PERM, uint32_t TM, bool NL = false, uint32_t MODE = kLaneSolve>
 struct LaneHub {
     static_assert(!(NL && MODE != kLaneSolve), "memo rows: linear run times only");
 #ifdef MR_STAMPS
-    unsigned long long lst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lst_last = 0;
+    mutable unsigned long long lst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lst_last = 0;
 #endif
     static constexpr bool kWin = MODE == kLaneWin || MODE == kLaneStage || MODE == kLaneQuery;  // destinations read the winner table
     static constexpr bool kRow = MODE == kLaneMemo || kWin;               // the table is a memo row
@@ -397,7 +451,23 @@ struct LaneHub {
         y = e == 0 ? sy : ry;
     }
     // region row entry r of entry p's cell (p = 0: the source)
-    __device__ __forceinline__ uint2 near_of(uint32_t p, uint32_t r) const { return p == 0 ? srow[r] : nearS[p * nreg + r]; }
+    // (kLaneQuery: a branch and an address space per arm; one pointer selected from the two
+    // is generic, and a generic load in the command loop makes every wait there one for zero)
+    __device__ __forceinline__ uint2 near_of(uint32_t p, uint32_t r) const {
+        if constexpr (MODE == kLaneQuery) {
+            uint2 e;
+            if (p == 0) {  // (used, so waited for, inside the arm: the LDS arm's waits stay counted)
+                e = gload64(srow + r);
+                e.x = vvolatile(e.x);
+                e.y = vvolatile(e.y);
+            } else {
+                e = lload64(nearS + p * nreg + r);
+            }
+            return e;
+        } else {
+            return p == 0 ? srow[r] : nearS[p * nreg + r];
+        }
+    }
     // entry e's label (run-time e; a select per entry: the rare paths only)
     __device__ __forceinline__ LLab get(uint32_t e) const {
         if constexpr (kRow) {
@@ -513,7 +583,8 @@ struct LaneHub {
                 yt = int(lm_nt(y)) - 1;
             }
         }
-        atomicOr(counter + kCtrFlags, kErrChain);
+        if constexpr (MODE == kLaneQuery) gatomic_or(counter + kCtrFlags, kErrChain);
+        else atomicOr(counter + kCtrFlags, kErrChain);
         return res;
     }
 
@@ -949,6 +1020,136 @@ struct LaneHub {
         return true;
     }
 
+    // kLaneQuery: emit for one record of a chunk (DESIGN.md section 3a''').  Every lane of
+    // the wave comes here once per chunk, whatever its record is: `skip` lanes (no record,
+    // or a source handed to the fallback) write nothing, `nopath` lanes the record of a cell
+    // no walk reaches.  Plans of 1 .. kLaneRowSlots command slots assemble the row in
+    // registers: the walk runs from the last command to the first, so each command is pushed
+    // in at slot 0 and the ones before it move up a slot, and after the walk command i sits
+    // in slot i with zeros behind the last.  The walk itself then issues no vector-memory
+    // instruction (a long label's commands go to the pool from inside it, behind a branch),
+    // and the chunk's stores are one straight-line block after it, the result and the slots,
+    // so the compiler can count them: the waits for the next chunks' loads, issued before
+    // this block, then leave these stores in flight.  Wider plans keep the slots' stores
+    // inside the walk.  All accesses go by address space.  q0: the chunk's first record
+    // (wave-uniform).
+    // Returns the records written (0 or 1).
+    __device__ __forceinline__ uint32_t emit_q(const LLab x, uint32_t xid, const Own xo, uint32_t qi, uint32_t q0, bool skip,
+                                               bool nopath) const {
+        const DevParams &p = P;
+        const uint32_t mc = __builtin_amdgcn_readfirstlane(p.max_cmds);
+        const bool fixed = mc >= 1u && mc <= kLaneRowSlots;
+        OutCmd *slots = a->out_cmd + (unsigned long long)qi * mc;
+        uint32_t len = lm_len(x.m);
+        uint32_t legs = metric(x, 0), money = metric(x, 1), time = metric(x, 2);
+        uint32_t word = (16u << 16) | (len & 0xFFFFu);
+        bool norow = skip;
+        if (nopath) {  // no boundary can walk here: cannot happen on a connected grid
+            legs = money = time = 0u;
+            word = uint32_t(16 + 1) << 16;
+            norow = true;
+        }
+        // where put() stores a command directly: the pool, or a row wider than the registers'
+        OutCmd *oc = fixed ? nullptr : slots;
+        uint32_t rk[kLaneRowSlots], rf[kLaneRowSlots], rt[kLaneRowSlots];
+#pragma unroll
+        for (uint32_t s = 0; s < kLaneRowSlots; ++s) rk[s] = rf[s] = rt[s] = 0u;
+        if (!norow && len > mc) {  // the overflow pool, else MR_ERR_CAPACITY
+            // (used, so waited for, inside the arm: else the wait stands where the arms join)
+            const uint32_t off = vvolatile(gatomic_add(counter + kCtrOvf, len));
+            if (mc == 0 || off + len > a->ovf_cap || off + len < off) {
+                word = (uint32_t(16 - 4) << 16) | (len & 0xFFFFu);
+                norow = true;
+            } else {
+                if (fixed) {
+                    rk[0] = kOvfTag;
+                    rf[0] = off;
+                    rt[0] = len;
+                } else {
+                    gstore16(slots, kOvfTag, off, len, 0u);
+                }
+                oc = a->ovf + off;
+                word = (uint32_t(16 + kStatusOverflow) << 16) | (len & 0xFFFFu);
+            }
+        }
+        int at = norow ? -1 : int(len) - 1;
+        uint32_t e = x.m;
+        int ox = xo.x, oy = xo.y;
+        uint32_t ork = xo.rk, orid = xo.rid, oc5 = xo.c5;
+        uint32_t eid = norow ? 0u : xid;
+        auto put_q = [&](int i, const Cmd &c) {
+            if (oc) {
+                gstore16(oc + i, c.kp, c.from, c.to, 0u);
+            } else {
+#pragma unroll
+                for (uint32_t s = kLaneRowSlots - 1u; s > 0; --s) {
+                    rk[s] = rk[s - 1u];
+                    rf[s] = rf[s - 1u];
+                    rt[s] = rt[s - 1u];
+                }
+                rk[0] = c.kp;
+                rf[0] = c.from;
+                rt[0] = c.to;
+            }
+        };
+        for (uint32_t guard = 0; at >= 0 && guard <= TM + 1; ++guard) {
+            const Own eo{ox, oy, ork, orid, oc5};
+            if (lm_nt(e) == 2 && at >= 0) {
+                const Cmd c = tail(e, eo, 1);
+                put_q(at--, c);
+            }
+            if (at >= 0) {
+                const Cmd c = tail(e, eo, 0);
+                put_q(at--, c);
+            }
+            eid = lm_par(e);
+            if (eid == 0) break;
+            e = meta_of(eid);
+            const Own n = own_of(eid);
+            ox = n.x;
+            oy = n.y;
+            ork = n.rk;
+            orid = n.rid;
+            oc5 = n.c5;
+        }
+        if (at != -1 || eid != 0) gatomic_or(counter + kCtrFlags, kErrChain);
+        // The chunk's records as two buffers of their exact size (q0: the chunk's first
+        // record): a lane without a result, a record without a row and the slots from
+        // max_cmds on (all of them in a plan whose rows the walk stored) take an offset past
+        // the buffer's end, which the range check drops, so the block is the same
+        // 1 + kLaneRowSlots instructions for every chunk and stands behind no branch.
+        const uint32_t nrec = min(64u, a->nq_lane - q0), lane = qi - q0;
+        const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc(a->out_res + q0, 0, int(nrec * 16u), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rcmd =
+            __builtin_amdgcn_make_buffer_rsrc(a->out_cmd + (unsigned long long)q0 * mc, 0, int(nrec * mc * 16u), 0x00020000);
+        bstore16(rres, skip ? kLaneDrop : lane * 16u, legs, money, time, word);
+        // Rows of kLaneRowSlots slots (64 bytes) leave whole: the lanes of a quad exchange
+        // their rows' slots (quad_transpose), so that in store s lane i of quad g holds slot i
+        // of the record of the quad's lane s, and the quad's four lanes write that record's
+        // row as one line, 16 lines an instruction, where a lane writing its own row's slot s
+        // touches a quarter of each of 64 lines.  Narrower rows are stored by their own lanes.
+        // (Both through the same instructions, selected bit by bit on a mask in a register:
+        // left to the compiler, the uniform choice becomes branches round the stores, and
+        // the stores of a chunk are no longer one count.)
+        const uint32_t whole = vmask(mc == kLaneRowSlots);
+        uint32_t tk[kLaneRowSlots], tf[kLaneRowSlots], tt[kLaneRowSlots];
+#pragma unroll
+        for (uint32_t s = 0; s < kLaneRowSlots; ++s) tk[s] = rk[s], tf[s] = rf[s], tt[s] = rt[s];
+        quad_transpose(tk);
+        quad_transpose(tf);
+        quad_transpose(tt);
+        const unsigned long long nomask = __ballot(norow);
+#pragma unroll
+        for (uint32_t s = 0; s < kLaneRowSlots; ++s) {
+            const uint32_t rec = (lane & ~3u) | s;  // (whole: the record whose row this lane helps to store)
+            const uint32_t drop = msel(whole, vmask(((nomask >> (rec & 63u)) & 1ull) != 0), vmask(norow || !fixed || s >= mc));
+            const uint32_t off = msel(whole, rec * (kLaneRowSlots * 16u) + (lane & 3u) * 16u, (lane * mc + s) * 16u);
+            bstore16(rcmd, msel(drop, kLaneDrop, off), msel(whole, tk[s], rk[s]), msel(whole, tf[s], rf[s]), msel(whole, tt[s], rt[s]), 0u);
+        }
+        MR_LSTAMP(3);  // (3 in this mode: the label's walk and the record's stores)
+        return skip ? 0u : 1u;
+    }
+
     // A cell's special entry (kNone10: plain) and CellIndex rank.  On a grid in the
     // standard layout (mr_grid rank_std: every cell's rank is the closed form of its
     // position) the rank is arithmetic and the entry a scan of the specials' cells in
@@ -975,7 +1176,9 @@ struct LaneHub {
                 t = e.x == v ? e.y : t;
             }
         } else {
-            const uint2 c = cell[v];  // {sinfo, rank}
+            uint2 c;  // {sinfo, rank}
+            if constexpr (MODE == kLaneQuery) c = gload64(cell + v);
+            else c = cell[v];
             t = c.x & kNone10;
             r = c.y;
         }
@@ -1364,6 +1567,38 @@ struct LaneHub {
         if (NL && !unc && !(a->dbg_flags & 8u) && !walk_certain(bx, get(bx), wx, wy)) unc = true;
         return row;
     }
+    // kLaneQuery: dest for record qi, with the three kinds of destination joined before one
+    // emit_q, so that a chunk has one store block whatever its lanes' destinations are.
+    // (Under this mode's gate no row has a blocker and run times are linear: dest's two
+    // certifications have nothing to do.)  Returns the records written.
+    __device__ __forceinline__ uint32_t dest_q(uint32_t qi, uint32_t q0, uint32_t w, uint32_t e, bool skip) const {
+        const DevParams &p = P;
+        const int wx = int(w % p.S) - int(p.H), wy = int(w / p.S) - int(p.H);
+        uint32_t tw, wr;
+        cell_word(w, wx, wy, tw, wr);
+        LLab x = start();
+        uint32_t xid = kOwn;
+        Own xo{wx, wy, wr, kNone10, 0u};
+        bool nopath = false;
+        if (w == src) {
+            xo = Own{sx, sy, src_rk, kNone10, 0u};
+        } else if (tw != kNone10) {
+            x = get(tw);
+            xid = tw;
+            xo = own_of(tw);
+        } else {
+            uint32_t bx = kNone32;
+            x = inf();
+            const bool slow = e == kLaneWinNone;
+            if (!slow) win_walk(e, xo, x, bx);
+            if (__any(slow)) {
+                if (slow) best_walk(src != p.vc, xo, x, bx);
+            }
+            nopath = bx == kNone32;
+        }
+        MR_LSTAMP(2);  // (2 in this mode: the destination's label)
+        return emit_q(x, xid, xo, qi, q0, skip, nopath);
+    }
     // kLaneStage: read_off with whole command rows (DESIGN.md section 3a''').  The wave runs
     // the destination loop to its busiest lane's count; a lane with a query in the iteration
     // assembles the record's row in its own row of the wave's stage (emit<true>)
@@ -1506,34 +1741,39 @@ struct LaneHub {
     // cannot make a source uncertain, so the only fallback is the plain cell of no region:
     // every record of such a source comes here and writes nothing, and the lane with the
     // source's first record finds its index in q_begin and hands it over once.
+    // Every lane of a chunk's wave comes here (have: the lane has a record; without one its
+    // words are those of the plan's last record, and nothing is written for it), and goes on
+    // to the chunk's one store block in emit_q: a lane that left before it would leave the
+    // number of stores behind the chunk's prefetches open.
     // Returns the records written (0 or 1).
-    __device__ __forceinline__ uint32_t query_record(uint32_t q, uint32_t sv, uint32_t w, uint32_t r0, uint32_t ww,
-                                                     const uint4 *rows) {
+    __device__ __forceinline__ uint32_t query_record(bool have, uint32_t q, uint32_t q0, uint32_t sv, uint32_t w, uint32_t r0,
+                                                     uint32_t ww, const uint4 *rows) {
         source_cell(sv);
         uint32_t row = r0 == kLaneRegNone ? kNone32 : r0;
         wsh = row == kNone32 ? 0u : kLaneWinBits * row;
         wnone = ts == kNone10 ? 0u : kLaneWinNone;
         row = ts != kNone10 ? nreg + ts - 1u : row;
+        bool skip = !have;
         if (row == kNone32) {  // a plain cell of no region: cannot happen where the memo gate held
-            if (q == 0 || gload32(a->q_srcv + q - 1) != sv) {
+            if (have && (q == 0 || gload32(a->q_srcv + q - 1) != sv)) {
                 uint32_t lo = 0, hi = a->n_lane;  // q_begin[lo] <= q < q_begin[hi]
                 while (hi - lo > 1u) {
                     const uint32_t mid = lo + (hi - lo) / 2u;
-                    if (a->q_begin[mid] <= q) lo = mid;
+                    if (gload32(a->q_begin + mid) <= q) lo = mid;
                     else hi = mid;
                 }
                 push_fallback(a, counter, lo, kNone32);
+                lane_drain();
             }
-            return 0;
+            skip = true;  // (the lane stays for the chunk's stores, on region row 0)
+            row = 0;
         }
         R = rows + row * (lane_memo_row_words(TM) / 4u);
         const uint4 h = R[TM];
         done = h.x;
         bndm = h.y;
         blk = h.z;
-        bool unc = false;
-        dest<false>(q, w, ((ww >> wsh) & kLaneWinNone) | wnone, start(), src != P.vc, unc);
-        return 1u;
+        return dest_q(q, q0, w, ((ww >> wsh) & kLaneWinNone) | wnone, skip);
     }
     // kLaneMemo, the winner table's build: cell w's word, region row r's winner at bit
     // kLaneWinBits r.  The row's representative source stands for every source of the

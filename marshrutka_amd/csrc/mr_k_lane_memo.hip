@@ -79,6 +79,12 @@ __global__ __launch_bounds__(kBS, 4) void hub_lane_win_kernel(const KArgs *__res
 #ifndef MR_LANE_STAGE_WAVES
 #define MR_LANE_STAGE_WAVES 3
 #endif
+// kLaneQuery: the chunks a wave's source cells and destinations are loaded ahead of the chunk
+// it reads off (2; 1: in the iteration that issues the gathers they address, for the A/B of
+// DESIGN.md section 3a''')
+#ifndef MR_LANE_QUERY_DEPTH
+#define MR_LANE_QUERY_DEPTH 2
+#endif
 template <uint32_t PERM, uint32_t TM, uint32_t MODE>
 __global__ __launch_bounds__(kBS, MODE == kLaneStage ? MR_LANE_STAGE_WAVES : 4) void hub_lane_memo_kernel(const KArgs *__restrict__ a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -108,32 +114,54 @@ __global__ __launch_bounds__(kBS, MODE == kLaneStage ? MR_LANE_STAGE_WAVES : 4) 
         // records at a grid-wide stride, so the chunks in flight are neighbours in the
         // output.  A chunk's source cells and destinations (coalesced) and then its two
         // gathers (the source's region byte, the destination's winner word) are issued
-        // before the previous chunk's destinations are read off and stored.
+        // one chunk ahead of the chunk whose destinations are read off and stored, and the
+        // source cells and destinations that address them two chunks ahead: a chunk's
+        // iteration issues the indices of the chunk after next, then the next chunk's
+        // gathers from the indices the iteration before loaded, so no load is waited for
+        // in the iteration that issued it.  Every load is issued by every lane, a lane
+        // without a record (the plan's last chunk, a look-ahead past the wave's last
+        // chunk) taking the plan's last record: with the loads behind no branch and the
+        // stores one block per chunk (LaneHub::emit_q), the waits are counted ones and
+        // leave the chunk's stores in flight.
         const uint32_t nq = a->nq_lane, chunks = (nq + 63u) / 64u, nw = gridDim.x * (kBS / 64);
         const uint32_t *qsv = a->q_srcv, *qd = a->q_dst, *win = a->lane_win;
         const uint8_t *reg0 = a->lane_reg0;
         uint32_t c = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBS / 64) + (threadIdx.x >> 6));
-        uint32_t q = c * 64u + lane_id(), sv = 0, w = 0, r0 = 0, ww = 0;
-        bool have = c < chunks && q < nq;
-        if (have) {
-            sv = gload32(qsv + q);
-            w = gload32(qd + q);
-            r0 = gload8(reg0 + sv);
-            ww = gload32(win + w);
-        }
-        for (; c < chunks; c += nw) {
-            const uint32_t cq = q, csv = sv, cw = w, cr0 = r0, cww = ww;
-            const bool chave = have;
-            const uint32_t cn = c + nw;
-            q = cn * 64u + lane_id();
-            have = cn < chunks && q < nq;
-            if (have) {
-                sv = gload32(qsv + q);
-                w = gload32(qd + q);
-                r0 = gload8(reg0 + sv);
-                ww = gload32(win + w);
+        if (c < chunks) {  // (so nq >= 1)
+            const uint32_t last = nq - 1u;
+            uint32_t q = c * 64u + lane_id();
+            uint32_t sv = gload32(qsv + min(q, last)), w = gload32(qd + min(q, last));
+            uint32_t sv1 = gload32(qsv + min(q + nw * 64u, last)), w1 = gload32(qd + min(q + nw * 64u, last));
+            uint32_t r0 = gload8(reg0 + sv), ww = gload32(win + w);
+            // (the first chunk needs all of these at once anyway; with nothing in flight on
+            // entry, the loop's wait counts are those of its own iterations, not the fewer
+            // operations that follow a load on the way in from here)
+            lane_drain();
+            for (; c < chunks; c += nw) {
+#if MR_LANE_QUERY_DEPTH == 1
+                const uint32_t q1 = min(q + nw * 64u, last);
+                sv1 = gload32(qsv + q1), w1 = gload32(qd + q1);
+#else
+                const uint32_t q2 = min(q + 2u * nw * 64u, last);
+                const uint32_t sv2 = gload32(qsv + q2), w2 = gload32(qd + q2);
+#endif
+                const uint32_t r1 = gload8(reg0 + sv1), ww1 = gload32(win + w1);
+#ifdef MR_STAMPS
+                // (diagnostic builds wait here for the chunk's own gathers, to time the wait)
+                asm volatile("" ::"v"(r0), "v"(ww));
+                {
+                    const unsigned long long now_ = __builtin_amdgcn_s_memtime();
+                    H.lst[1] += now_ - H.lst_last;  // (1 in this mode: the loads and the wait for them)
+                    H.lst_last = now_;
+                }
+#endif
+                written += H.query_record(q < nq, q, c * 64u, sv, w, r0, ww, rows);
+                q += nw * 64u;
+                sv = sv1, w = w1, r0 = r1, ww = ww1;
+#if MR_LANE_QUERY_DEPTH != 1
+                sv1 = sv2, w1 = w2;
+#endif
             }
-            if (chave) written += H.query_record(cq, csv, cw, cr0, cww, rows);
         }
     } else if constexpr (MODE == kLaneStage) {  // whole waves: the rows' stores are the wave's
         H.STW = smem + lane_memo_lds_bytes(NS, nreg, TM) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kLaneStageWave;
