@@ -546,6 +546,66 @@ int mr_nearest_label_ex(mr_plan *plan, uint32_t i, uint32_t g, uint32_t r, mr_re
  * MR_ERR_INVALID_ARG for poi > MR_POI_FORUM or a null grid or n.  Needs no device. */
 int mr_grid_poi_cells(const mr_grid *grid, uint32_t poi, mr_cell_index *out, uint32_t cap, uint32_t *n);
 
+/* ---- tours: the best visiting order of up to 10 stops --------------------- */
+/* A tour is a start cell, n stops (0 <= n <= MR_TOUR_MAX_STOPS) and an end rule, one mode for
+ * the whole plan.  Tour t lists cells[tour_begin[t] .. tour_begin[t + 1]):
+ *   MR_TOUR_OPEN     start, stop 0 .. stop n-1; the trip ends at whichever stop comes last  (n legs)
+ *   MR_TOUR_RETURN   the same; the trip comes back to the start                        (n + 1 legs)
+ *   MR_TOUR_TO_LAST  start, the stops, then a fixed end cell that is not a stop        (n + 1 legs)
+ * The traveller stops at every stop, so the legs are separate routes: the cost of an order pi (a
+ * permutation of the stop positions 0..n-1) is the component-wise sum over its legs of the metrics
+ * of FindPath::eval(from, to), which are the matrix record of (from, to); a leg from a cell to
+ * itself costs (0, 0, 0).  The answer is the pi with the least
+ * (m[q0], m[q1], m[q2], pi[0], .., pi[n-1]), (q0, q1, q2) the parameters' metric order (sort_by
+ * completed as nearest plans complete it): ties on all three sums go to the lexicographically
+ * least sequence of positions.  Cells may repeat within a tour and between tours, and a stop may
+ * equal the start.
+ * Limit gate: a tour is answered only if, for each metric, n_legs x (the largest value of that
+ * metric over all ordered pairs of the tour's listed cells) <= 2^32 - 1, so that no sum the
+ * device forms can wrap.  Otherwise its record has status = MR_ERR_LIMIT, zero metrics and
+ * order[] all 0xFF (n_stops and n_legs stay the tour's); the plan's other tours are unaffected
+ * and the accessors still return MR_OK.
+ * The plan owns a matrix plan's state over the P distinct cells of all tours (sources and
+ * destinations both, row-major cell order): P x pitch(P) x 16 B on the device, which for tours
+ * that share few cells grows with the square of the tour count.  mr_plan_run enqueues the matrix
+ * pass and then the tour kernel's launches; mr_plan_run / _wait / _get_stats / _kernel_ms /
+ * _destroy apply.
+ * Errors, all argument checks before any device is touched (mr_last_error names the tour and the
+ * position): MR_ERR_INVALID_ARG for a null pointer, n_tours == 0, mode > 2, tour_begin[0] != 0 or
+ * offsets that decrease, a tour with no cell (fewer than 2 under MR_TOUR_TO_LAST) or more than
+ * MR_TOUR_MAX_STOPS stops; MR_ERR_INVALID_INDEX for a cell that is not a grid cell; MR_ERR_LIMIT
+ * when the internal matrix does not fit the device block cache's largest block (16 GiB: at
+ * most 32 768 distinct cells); MR_ERR_NO_DEVICE as for the other plans.  The
+ * mr_matrix_*, mr_nearest_*, mr_sssp_* and pair-plan accessors return MR_ERR_INVALID_ARG on a
+ * tour plan, the mr_tour_* accessors on any other plan.  MR_ERR_LIMIT for labels holds as
+ * stated at mr_status: the accessors that wait report it. */
+#define MR_TOUR_MAX_STOPS 10u
+enum { MR_TOUR_OPEN = 0, MR_TOUR_RETURN = 1, MR_TOUR_TO_LAST = 2 };
+typedef struct mr_tour_record {
+    uint32_t legs, money, time_s;      /* the winning order's sums */
+    int32_t  status;                   /* MR_OK or MR_ERR_LIMIT (the limit gate above) */
+    uint8_t  n_stops, n_legs;
+    uint8_t  order[MR_TOUR_MAX_STOPS]; /* order[r] = position of the r-th stop visited; 0xFF past n_stops */
+    uint32_t reserved;                 /* 0 */
+} mr_tour_record;                      /* 32 B: four a 128 B line */
+int mr_tour_plan_create(const mr_grid *grid, const mr_params *params, const mr_cell_index *cells,
+                        const uint32_t *tour_begin /* n_tours + 1 offsets into cells */, uint32_t n_tours,
+                        uint32_t mode, mr_plan **out);
+/* the records in the caller's tour order (waits); MR_ERR_CAPACITY if cap_records < n_tours */
+int mr_tour_records(mr_plan *plan, mr_tour_record *out, uint64_t cap_records);
+/* device records: [n_tours rounded up to 4] mr_tour_record in the caller's order, pad records
+ * zeros.  Waits for the passes enqueued so far; the next mr_plan_run rewrites them */
+int mr_tour_device_records(mr_plan *plan, void **d_records, uint64_t *bytes);
+/* leg r < n_legs of tour t's winning order rebuilt in full, as mr_matrix_label rebuilds a pair:
+ * MR_OK, MR_ERR_CAPACITY (out->n_commands > cap), MR_NOT_FOUND for a tour whose status is
+ * MR_ERR_LIMIT, MR_ERR_INVALID_ARG for t >= n_tours or r >= n_legs */
+int mr_tour_leg_label(mr_plan *plan, uint32_t t, uint32_t r, mr_result *out, mr_command *cmds, uint32_t cap);
+/* the distinct cells of all tours: the side of the plan's internal matrix */
+int mr_tour_num_points(const mr_plan *plan, uint32_t *n_points);
+/* the tour launches' time a pass, averaged over the window the last mr_plan_kernel_ms closed (as
+ * mr_plan_fill_ms); mr_plan_kernel_ms itself gives the matrix read-off's.  0 for any other plan */
+double mr_tour_kernel_ms(const mr_plan *plan);
+
 /* ---- misc ---------------------------------------------------------------- */
 uint32_t mr_abi_version(void);
 /* Human-readable description of the last error on this thread. */

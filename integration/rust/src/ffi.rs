@@ -159,6 +159,28 @@ pub struct mr_nearest_record {
 /// The largest `k` of `mr_nearest_plan_create_ex` (one list entry per lane of a wave).
 pub const MR_NEAREST_MAX_K: u32 = 64;
 
+/// A tour plan's record: the winning order's sums, `status` (`MR_OK`, or `MR_ERR_LIMIT` with zero
+/// sums and `order` all 0xFF for a tour the limit gate refused), and `order[r]` = the position of
+/// the r-th stop visited (0xFF past `n_stops`).
+#[repr(C)]
+#[derive(Copy, Clone, Default, Debug)]
+pub struct mr_tour_record {
+    pub legs: u32,
+    pub money: u32,
+    pub time_s: u32,
+    pub status: i32,
+    pub n_stops: u8,
+    pub n_legs: u8,
+    pub order: [u8; 10],
+    pub reserved: u32,
+}
+
+/// The most stops of a tour, and a tour plan's end rules (`mode` of `mr_tour_plan_create`).
+pub const MR_TOUR_MAX_STOPS: u32 = 10;
+pub const MR_TOUR_OPEN: u32 = 0;
+pub const MR_TOUR_RETURN: u32 = 1;
+pub const MR_TOUR_TO_LAST: u32 = 2;
+
 /// Opaque handles.
 pub enum mr_grid {}
 pub enum mr_plan {}
@@ -263,6 +285,16 @@ extern "C" {
     pub fn mr_nearest_label_ex(plan: *mut mr_plan, i: u32, g: u32, r: u32, out: *mut mr_result, cmds: *mut mr_command,
                                cap: u32) -> c_int;
     pub fn mr_grid_poi_cells(grid: *const mr_grid, poi: u32, out: *mut mr_cell_index, cap: u32, n: *mut u32) -> c_int;
+    // tours: the best visiting order of up to MR_TOUR_MAX_STOPS stops; tour t lists
+    // cells[tour_begin[t] .. tour_begin[t + 1]): the start, the stops, under MR_TOUR_TO_LAST the end
+    pub fn mr_tour_plan_create(grid: *const mr_grid, params: *const mr_params, cells: *const mr_cell_index,
+                               tour_begin: *const u32, n_tours: u32, mode: u32, out: *mut *mut mr_plan) -> c_int;
+    pub fn mr_tour_records(plan: *mut mr_plan, out: *mut mr_tour_record, cap_records: u64) -> c_int;
+    pub fn mr_tour_device_records(plan: *mut mr_plan, d_records: *mut *mut c_void, bytes: *mut u64) -> c_int;
+    pub fn mr_tour_leg_label(plan: *mut mr_plan, t: u32, r: u32, out: *mut mr_result, cmds: *mut mr_command,
+                             cap: u32) -> c_int;
+    pub fn mr_tour_num_points(plan: *const mr_plan, n_points: *mut u32) -> c_int;
+    pub fn mr_tour_kernel_ms(plan: *const mr_plan) -> f64;
 
     // misc
     pub fn mr_abi_version() -> u32;

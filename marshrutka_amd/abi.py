@@ -91,12 +91,23 @@ class mr_nearest_record(C.Structure):
 NEAREST_NONE = 0xFFFFFFFF  # mr_nearest_record.dst of an empty group (k-nearest: or of an empty rank)
 MR_NEAREST_MAX_K = 64      # the largest k of mr_nearest_plan_create_ex
 
+TOUR_MAX_STOPS = 10        # MR_TOUR_MAX_STOPS: the most stops of a tour
+TOUR_OPEN, TOUR_RETURN, TOUR_TO_LAST = 0, 1, 2  # MR_TOUR_*: a tour plan's end rule
+
+
+class mr_tour_record(C.Structure):
+    _fields_ = [("legs", C.c_uint32), ("money", C.c_uint32), ("time_s", C.c_uint32), ("status", C.c_int32),
+                ("n_stops", C.c_uint8), ("n_legs", C.c_uint8), ("order", C.c_uint8 * TOUR_MAX_STOPS),
+                ("reserved", C.c_uint32)]
+
+
 assert C.sizeof(mr_cell_index) == 8
 assert C.sizeof(mr_cell) == 16
 assert C.sizeof(mr_command) == 40
 assert C.sizeof(mr_result) == 32
 assert C.sizeof(mr_query) == 16
 assert C.sizeof(mr_nearest_record) == 32
+assert C.sizeof(mr_tour_record) == 32
 
 
 # ---- value types -------------------------------------------------------------

@@ -266,6 +266,21 @@ struct KArgs {
     uint32_t nr_nchunk;
     uint32_t nr_k;
 };
+// Tour plans (DESIGN.md section 3b''''): tour_kernel's argument block, passed by value, one a
+// launch.  The plan's matrix rows are both its input (mx_rows: a 16 B record per ordered pair of
+// the plan's points, point p's row row_of_point[p], its column p) and what the matrix pass before
+// it on the stream wrote.  tours[k] = {first entry of cells[], entries, the caller's tour (its
+// record), 0} for the plan's tours sorted by size class; cells[] holds point indices.  A launch
+// takes tours [first, first + count), none with more than nmax stops (the LDS slot's size).
+// records: two uint4 a record (mr_tour_record), the caller's order.
+struct TourArgs {
+    const uint4 *rows;
+    const uint32_t *row_of_point;
+    const uint16_t *cells;
+    const uint4 *tours;
+    uint4 *records;
+    uint32_t pitch, mode, first, count, nmax;
+};
 // KArgs::all_mode: a cell word per (source, cell), a record per (source, listed destination),
 // or a record per (source, group of listed destinations)
 constexpr uint32_t kAllCells = 1u, kAllMatrix = 2u, kAllNearest = 3u;

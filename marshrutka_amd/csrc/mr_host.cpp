@@ -43,6 +43,9 @@ hipError_t launch_nearest(const KArgs *d_args, const uint32_t perm[3], uint32_t 
 int nearest_blocks_per_cu(const uint32_t perm[3]);
 hipError_t launch_knearest(const KArgs *d_args, const uint32_t perm[3], uint32_t gx, hipStream_t stream);
 int knearest_blocks_per_cu(const uint32_t perm[3]);
+uint32_t tour_lds_bytes(uint32_t nmax, bool wave);
+hipError_t launch_tour(const TourArgs &ta, const uint32_t perm[3], bool wave, uint32_t gx, hipStream_t stream);
+int tour_blocks_per_cu(const uint32_t perm[3], bool wave, uint32_t nmax);
 hipError_t launch_hub_fill(const KArgs *hub_args, const KArgs *fill_args, const uint32_t perm[3], uint32_t spw,
                            uint32_t hub_blocks, uint32_t fill_blocks, uint32_t lds_bytes, hipStream_t stream);
 int hub_fill_blocks_per_cu(const uint32_t perm[3], uint32_t spw, uint32_t lds_bytes);
@@ -1601,6 +1604,9 @@ struct mr_plan {
     // a nearest plan: a matrix plan (matrix is set too: no cell words, serial launches, one
     // slot) whose rows hold one record per destination group (Nearest below)
     bool nearest = false;
+    // a tour plan: a matrix plan over the tours' distinct cells (matrix is set too), reduced on
+    // the device to one record a tour by the tour launches that follow each pass (Tour below)
+    bool tour = false;
     bool grid_in_lds = false;
     uint32_t algo = kAlgoGeneric;
     uint32_t blocks = 0, cus = 256;
@@ -1608,6 +1614,7 @@ struct mr_plan {
     bool fb_none = false;                 // a completed pass of this plan had no fallback sources
     uint32_t runs = 0;
     double fill_ms = 0.0;                 // all-destinations: average fill launch of the last window
+    double tour_ms = 0.0;                 // tour plans: average of a pass's tour launches, the last window
 
     Stream stream;      // the plan's own
     Stream hub_stream;  // overlap on two streams: the specials' solves of every slot
@@ -1628,8 +1635,12 @@ struct mr_plan {
     std::vector<FillTimed> timed_fill;  // all-destinations: fill launches
     // timings of event pairs already folded (a caller that never asks for kernel_ms
     // must not pile up events: mr_plan_run folds the oldest beyond kMaxTimed)
-    double acc_ms = 0.0, acc_fill_ms = 0.0;
-    uint32_t acc_n = 0, acc_fill_n = 0;
+    double acc_ms = 0.0, acc_fill_ms = 0.0, acc_tour_ms = 0.0;
+    uint32_t acc_n = 0, acc_fill_n = 0, acc_tour_n = 0;
+    // tour plans: the event pair round each pass's tour launches.  A hub pass's fill pair ends
+    // at `first` (the matrix read-off's time stays its own), so these are folded after
+    // timed_fill, and no more of them
+    std::vector<TimedPass> timed_tour;
 
     // the map's tables: views of the grid's shared copies, or of the plan's own where the
     // grid's live on another device; the special table and the caravan hubs
@@ -1684,6 +1695,25 @@ struct mr_plan {
         DevBuf<uint4> chunk;
         uint32_t n_groups = 0, k = 1;
     } nr;
+    // tour plans: the plan's points are mx.dst_v (the distinct cells of all tours in row-major
+    // cell order, sources and destinations both).  cells: the caller's cell list as point
+    // indices; tours: {first entry of cells, entries, the caller's tour, 0} sorted by size
+    // class; records: two uint4 a record, the caller's order, n_tours rounded up to 4 (pad:
+    // zeros, written once).  A launch per non-empty size class.
+    struct Tour {
+        DevBuf<uint16_t> cells;
+        DevBuf<uint32_t> row_of_point;
+        DevBuf<uint4> tours, records;
+        std::vector<uint32_t> begin;       // the caller's offsets (n_tours + 1)
+        std::vector<uint16_t> cells_h;     // the caller's cells as point indices
+        uint32_t n_tours = 0, mode = 0;
+        struct Launch {
+            TourArgs args;
+            bool wave;
+            uint32_t gx;
+        };
+        std::vector<Launch> launches;
+    } tr;
     struct Hub {
         uint32_t n_lane = 0;               // sources on the lane kernel; the rest on hub_kernel
         uint32_t lane_g = 0;               // > 0: the n_lane sources run G lanes each (hub_group_kernel)
@@ -3081,6 +3111,22 @@ static hipError_t run_hub(mr_plan *pl, hipStream_t s) {
     return e;
 }
 
+// a tour plan's launches behind its matrix pass, a class each, in stream order; the pair of
+// events round them is the plan's (timed_tour)
+static hipError_t run_tours(mr_plan *pl, hipStream_t s) {
+    Event t0, t1;
+    if (t0.create() != hipSuccess || t1.create() != hipSuccess) return hipErrorUnknown;
+    (void)hipEventRecord(t0.get(), s);
+    // the matrix read-off's pair ends where the tour launches begin
+    if (!pl->timed_fill.empty() && !pl->timed_fill.back().second) pl->timed_fill.back().second = t0.get();
+    hipError_t e = hipSuccess;
+    for (const mr_plan::Tour::Launch &l : pl->tr.launches)
+        if (e == hipSuccess) e = launch_tour(l.args, pl->ka.p.perm, l.wave, l.gx, s);
+    (void)hipEventRecord(t1.get(), s);
+    pl->timed_tour.push_back({std::move(t0), std::move(t1)});
+    return e;
+}
+
 extern "C" int mr_plan_run(mr_plan *pl, void *stream) {
     if (!pl) return fail(MR_ERR_INVALID_ARG, "null plan");
     hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : pl->stream.get();
@@ -3117,6 +3163,7 @@ extern "C" int mr_plan_run(mr_plan *pl, void *stream) {
     // raw outputs for a collective: the overflow pool in record order (byte-deterministic)
     if (e == hipSuccess && pl->out.ovf_order && !pl->all_mode)
         e = launch_ovf_order(pl->cur().args.get(), nrec_of(pl->hp), pl->out.ovf_tmp.get(), s);
+    if (e == hipSuccess && pl->tour) e = run_tours(pl, s);
     (void)hipEventRecord(e1.get(), s);
     // the pass's end event doubles as the plan's last event (plan_sync): a record of
     // its own cost ~6 us of command-processor time per pass.  `timed` owns it from here.
@@ -3166,6 +3213,17 @@ static void fold_timed(mr_plan *pl, size_t keep) {
         }
     }
     pl->timed_fill.erase(pl->timed_fill.begin(), pl->timed_fill.begin() + ptrdiff_t(nf));
+    const size_t nt = pl->timed_tour.size() > keep ? pl->timed_tour.size() - keep : 0;
+    for (size_t i = 0; i < nt; ++i) {
+        auto &e = pl->timed_tour[i];
+        float ms = 0.f;
+        if (hipEventSynchronize(e.second.get()) == hipSuccess &&
+            hipEventElapsedTime(&ms, e.first.get(), e.second.get()) == hipSuccess) {
+            pl->acc_tour_ms += ms;
+            ++pl->acc_tour_n;
+        }
+    }
+    pl->timed_tour.erase(pl->timed_tour.begin(), pl->timed_tour.begin() + ptrdiff_t(nt));
     const size_t n = pl->timed.size() > keep ? pl->timed.size() - keep : 0;
     for (size_t i = 0; i < n; ++i) {
         auto &e = pl->timed[i];
@@ -3186,6 +3244,9 @@ extern "C" double mr_plan_kernel_ms(mr_plan *pl, uint32_t *n_launches) {
     // all-destinations passes: the fill launches' own time (their end event is the pass's)
     fold_timed(pl, 0);
     pl->fill_ms = pl->acc_fill_n ? pl->acc_fill_ms / pl->acc_fill_n : 0.0;
+    pl->tour_ms = pl->acc_tour_n ? pl->acc_tour_ms / pl->acc_tour_n : 0.0;
+    pl->acc_tour_ms = 0.0;
+    pl->acc_tour_n = 0;
     // (a matrix plan's main kernel is its read-off: the matrix launches of the hub passes)
     const bool mx = pl->matrix && pl->acc_fill_n;
     const double tot = mx ? pl->acc_fill_ms : pl->acc_ms;
@@ -4356,7 +4417,7 @@ extern "C" int mr_matrix_plan_create(const mr_grid *g, const mr_params *prm, con
 
 // a matrix plan whose last pass raised no device error (waits for the plan)
 static int matrix_plan(mr_plan *pl) {
-    if (!pl || !pl->matrix || pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest || pl->tour) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     uint32_t flags = 0;
     return check_device_errors(pl, flags);
 }
@@ -4385,7 +4446,7 @@ extern "C" int mr_matrix_records(mr_plan *pl, mr_label_record *out, uint64_t cap
 }
 
 extern "C" int mr_matrix_device_records(mr_plan *pl, void **d_records, uint64_t *bytes) {
-    if (!pl || !pl->matrix || pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest || pl->tour) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // whole records behind the pointer
     if (d_records) *d_records = pl->mx.rows.get();
     if (bytes) *bytes = uint64_t(pl->ka.nsrc) * pl->mx.pitch * sizeof(mr_label_record);
@@ -4393,22 +4454,22 @@ extern "C" int mr_matrix_device_records(mr_plan *pl, void **d_records, uint64_t 
 }
 
 extern "C" int mr_matrix_record_pitch(mr_plan *pl, uint32_t *records_per_row) {
-    if (!pl || !pl->matrix || pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest || pl->tour) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     if (!records_per_row) return fail(MR_ERR_INVALID_ARG, "null output");
     *records_per_row = pl->mx.pitch;
     return MR_OK;
 }
 
 extern "C" int mr_matrix_source_rows(const mr_plan *pl, uint32_t *row_of_source, uint32_t n_src) {
-    if (!pl || !pl->matrix || pl->nearest) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest || pl->tour) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     if (n_src && !row_of_source) return fail(MR_ERR_INVALID_ARG, "null output");
     for (uint32_t i = 0; i < n_src; ++i) row_of_source[i] = i < pl->src_of_input.size() ? pl->src_of_input[i] : kNone32;
     return MR_OK;
 }
 
-extern "C" int mr_matrix_label(mr_plan *pl, uint32_t i, uint32_t j, mr_result *res, mr_command *cmds, uint32_t cap) {
-    if (int st = matrix_plan(pl)) return st;
-    if (!res) return fail(MR_ERR_INVALID_ARG, "null result");
+// the label of the caller's source i x destination j of a plan that holds matrix rows, rebuilt
+// from its record and the source's table (mr_matrix_label; a tour plan's legs)
+static int matrix_label_at(mr_plan *pl, uint32_t i, uint32_t j, mr_result *res, mr_command *cmds, uint32_t cap) {
     const mr_plan::Matrix &m = pl->mx;
     if (i >= m.n_src || j >= m.n_dst) return fail(MR_ERR_INVALID_ARG, "matrix index");
     const uint32_t si = pl->src_of_input[i], w = m.dst_v[j];
@@ -4441,6 +4502,12 @@ extern "C" int mr_matrix_label(mr_plan *pl, uint32_t i, uint32_t j, mr_result *r
     for (size_t q = 0; q < seq.size(); ++q)
         if (!expand_cmd(pl->grid, cs, seq[q], cmds[q])) return fail(MR_ERR_DEVICE, "command names no cell");
     return MR_OK;
+}
+
+extern "C" int mr_matrix_label(mr_plan *pl, uint32_t i, uint32_t j, mr_result *res, mr_command *cmds, uint32_t cap) {
+    if (int st = matrix_plan(pl)) return st;
+    if (!res) return fail(MR_ERR_INVALID_ARG, "null result");
+    return matrix_label_at(pl, i, j, res, cmds, cap);
 }
 
 // ------------------------------------------------------------ nearest of a set
@@ -4609,3 +4676,185 @@ extern "C" int mr_grid_poi_cells(const mr_grid *g, uint32_t poi, mr_cell_index *
     if (k > cap) return fail(MR_ERR_CAPACITY, "mr_grid_poi_cells: " + std::to_string(k) + " cells, room for " + std::to_string(cap));
     return MR_OK;
 }
+
+// ------------------------------------------------------------ tours
+// MR_TOUR_WAVE_MAX: tours of at most this many stops take a wave each (0: none does, every
+// tour takes a workgroup).  Four wave slots of more than 8 stops do not fit a CU's LDS.
+static uint32_t tour_wave_max() {
+    if (const char *e = std::getenv("MR_TOUR_WAVE_MAX")) return uint32_t(std::min(8, std::max(0, std::atoi(e))));
+    return 5u;
+}
+
+// the tour state of a matrix plan over the points: the cell lists as point indices, the tours by
+// size class, the records (zeroed once: the pad records stay zeros) and a launch a class
+static int plan_tours(mr_plan *pl, const std::vector<uint32_t> &cell_v, const uint32_t *tour_begin, uint32_t n_tours,
+                      uint32_t mode) {
+    mr_plan::Tour &tr = pl->tr;
+    const std::vector<uint32_t> &points = pl->mx.dst_v;
+    tr.n_tours = n_tours;
+    tr.mode = mode;
+    tr.begin.assign(tour_begin, tour_begin + n_tours + 1);
+    tr.cells_h.resize(cell_v.size());
+    for (size_t i = 0; i < cell_v.size(); ++i)
+        tr.cells_h[i] = uint16_t(std::lower_bound(points.begin(), points.end(), cell_v[i]) - points.begin());
+    const uint32_t wave_max = tour_wave_max();
+    const auto stops = [&](uint32_t t) { return tr.begin[t + 1] - tr.begin[t] - (mode == MR_TOUR_TO_LAST ? 2u : 1u); };
+    // a wave a tour up to wave_max stops; a workgroup a tour up to 8 (a table of 24 KB) and beyond
+    const auto cls = [&](uint32_t n) { return wave_max && n <= wave_max ? 0u : (n <= 8u ? 1u : 2u); };
+    std::vector<uint32_t> by_class(n_tours);
+    for (uint32_t t = 0; t < n_tours; ++t) by_class[t] = t;
+    // (within a class the longest first: a unit's stride then mixes long and short tours)
+    std::stable_sort(by_class.begin(), by_class.end(), [&](uint32_t x, uint32_t y) {
+        const uint32_t nx = stops(x), ny = stops(y);
+        return cls(nx) != cls(ny) ? cls(nx) < cls(ny) : nx > ny;
+    });
+    std::vector<uint4> tours(n_tours);
+    for (uint32_t k = 0; k < n_tours; ++k) {
+        const uint32_t t = by_class[k];
+        tours[k] = make_uint4(tr.begin[t], tr.begin[t + 1] - tr.begin[t], t, 0u);
+    }
+    const size_t nrec = (size_t(n_tours) + 3) / 4 * 4;
+    if (upload(tr.cells, tr.cells_h) != hipSuccess || upload(tr.row_of_point, pl->src_of_input) != hipSuccess ||
+        upload(tr.tours, tours) != hipSuccess || tr.records.alloc_zero(nrec * 2) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "hipMalloc tour tables");
+    for (uint32_t k = 0; k < n_tours;) {
+        const uint32_t c = cls(stops(by_class[k]));
+        uint32_t e = k;
+        while (e < n_tours && cls(stops(by_class[e])) == c) ++e;
+        mr_plan::Tour::Launch l{};
+        l.wave = c == 0u;
+        l.args.rows = pl->mx.rows.get();
+        l.args.row_of_point = tr.row_of_point.get();
+        l.args.cells = tr.cells.get();
+        l.args.tours = tr.tours.get();
+        l.args.records = tr.records.get();
+        l.args.pitch = pl->mx.pitch;
+        l.args.mode = mode;
+        l.args.first = k;
+        l.args.count = e - k;
+        l.args.nmax = stops(by_class[k]);  // the class's longest tour: its LDS, not the class bound's
+        const int per_cu = tour_blocks_per_cu(pl->ka.p.perm, l.wave, l.args.nmax);
+        if (per_cu <= 0) return fail(MR_ERR_DEVICE, "tour kernel: no workgroup fits a CU");
+        const uint64_t units = l.wave ? (uint64_t(l.args.count) + 3) / 4 : l.args.count;
+        l.gx = resident_grid(units, uint64_t(per_cu) * pl->cus);
+        if (const char *g = std::getenv("MR_TOUR_GX")) l.gx = uint32_t(std::max(1, std::atoi(g)));
+        tr.launches.push_back(l);
+        k = e;
+    }
+    return MR_OK;
+}
+
+extern "C" int mr_tour_plan_create(const mr_grid *g, const mr_params *prm, const mr_cell_index *cells,
+                                   const uint32_t *tour_begin, uint32_t n_tours, uint32_t mode, mr_plan **out) {
+    if (!g || !prm || !out || !cells || !tour_begin) return fail(MR_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!n_tours) return fail(MR_ERR_INVALID_ARG, "a tour plan needs at least one tour");
+    if (mode > MR_TOUR_TO_LAST) return fail(MR_ERR_INVALID_ARG, "tour mode " + std::to_string(mode) + " is not an MR_TOUR_* value");
+    if (tour_begin[0] != 0) return fail(MR_ERR_INVALID_ARG, "tour 0 position 0: tour_begin[0] is not 0");
+    const uint32_t fixed = mode == MR_TOUR_TO_LAST ? 2u : 1u;  // the cells of a tour that are not stops
+    for (uint32_t t = 0; t < n_tours; ++t) {
+        const std::string at = "tour " + std::to_string(t) + " position " + std::to_string(tour_begin[t]) + ": ";
+        if (tour_begin[t + 1] < tour_begin[t]) return fail(MR_ERR_INVALID_ARG, at + "its end offset is below its first");
+        const uint32_t c = tour_begin[t + 1] - tour_begin[t];
+        if (c < fixed)
+            return fail(MR_ERR_INVALID_ARG, at + std::to_string(c) + " cells, a tour of this mode lists at least " + std::to_string(fixed));
+        if (c - fixed > MR_TOUR_MAX_STOPS)
+            return fail(MR_ERR_INVALID_ARG, at + std::to_string(c - fixed) + " stops, more than MR_TOUR_MAX_STOPS = " +
+                                                std::to_string(MR_TOUR_MAX_STOPS));
+    }
+    const uint32_t n_cells = tour_begin[n_tours];
+    std::vector<uint32_t> cell_v(n_cells);
+    for (uint32_t t = 0; t < n_tours; ++t)
+        for (uint32_t i = tour_begin[t]; i < tour_begin[t + 1]; ++i)
+            if (!g->find(cells[i], cell_v[i]))
+                return fail(MR_ERR_INVALID_INDEX, "tour " + std::to_string(t) + " position " + std::to_string(i - tour_begin[t]) +
+                                                      " is not a grid cell");
+    if (!mr_device_available()) return fail(MR_ERR_NO_DEVICE, "no gfx950 device visible (no CPU fallback)");
+    // the points: the distinct cells in row-major order, sources and destinations both
+    std::vector<uint32_t> points(cell_v);
+    std::sort(points.begin(), points.end());
+    points.erase(std::unique(points.begin(), points.end()), points.end());
+    const uint64_t P = points.size(), pitch = (P + 7) / 8 * 8;
+    if (P > 0x10000ull || P * pitch > kMatrixMaxBytes / sizeof(mr_label_record))
+        return fail(MR_ERR_LIMIT, "tour plan: the matrix of its " + std::to_string(P) +
+                                      " distinct cells exceeds the device block cache's largest block");
+    std::vector<mr_query> qs(points.size());
+    for (size_t i = 0; i < points.size(); ++i) qs[i].from = qs[i].to = g->idx[points[i]];
+    std::vector<uint32_t> dv(points);
+    int st = plan_create(g, prm, qs.data(), uint32_t(points.size()), 16, out, true, &dv);
+    if (st != MR_OK) return st;
+    mr_plan *pl = *out;
+    pl->mx.n_src = uint32_t(points.size());
+    pl->tour = true;
+    if ((st = plan_tours(pl, cell_v, tour_begin, n_tours, mode)) != MR_OK) {
+        const std::string msg = mr_last_error();
+        mr_plan_destroy(pl);
+        *out = nullptr;
+        return fail(st, msg);
+    }
+    return MR_OK;
+}
+
+// a tour plan whose last pass raised no device error (waits for the plan)
+static int tour_plan(mr_plan *pl) {
+    if (!pl || !pl->tour) return fail(MR_ERR_INVALID_ARG, "not a tour plan");
+    uint32_t flags = 0;
+    return check_device_errors(pl, flags);
+}
+
+extern "C" int mr_tour_records(mr_plan *pl, mr_tour_record *out, uint64_t cap_records) {
+    if (int st = tour_plan(pl)) return st;
+    if (!out) return fail(MR_ERR_INVALID_ARG, "null output");
+    if (cap_records < pl->tr.n_tours) return fail(MR_ERR_CAPACITY, "mr_tour_records: output shorter than n_tours");
+    if (hipMemcpy(out, pl->tr.records.get(), size_t(pl->tr.n_tours) * sizeof(mr_tour_record), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "copy tour records");
+    return MR_OK;
+}
+
+extern "C" int mr_tour_device_records(mr_plan *pl, void **d_records, uint64_t *bytes) {
+    if (!pl || !pl->tour) return fail(MR_ERR_INVALID_ARG, "not a tour plan");
+    if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // whole records behind the pointer
+    if (d_records) *d_records = pl->tr.records.get();
+    if (bytes) *bytes = (uint64_t(pl->tr.n_tours) + 3) / 4 * 4 * sizeof(mr_tour_record);
+    return MR_OK;
+}
+
+extern "C" int mr_tour_leg_label(mr_plan *pl, uint32_t t, uint32_t r, mr_result *res, mr_command *cmds, uint32_t cap) {
+    if (int st = tour_plan(pl)) return st;
+    if (!res) return fail(MR_ERR_INVALID_ARG, "null result");
+    const mr_plan::Tour &tr = pl->tr;
+    if (t >= tr.n_tours) return fail(MR_ERR_INVALID_ARG, "tour index");
+    mr_tour_record rec;
+    if (hipMemcpy(&rec, reinterpret_cast<const mr_tour_record *>(tr.records.get()) + t, sizeof(rec), hipMemcpyDeviceToHost) !=
+        hipSuccess)
+        return fail(MR_ERR_DEVICE, "copy tour record");
+    const uint32_t c = tr.begin[t + 1] - tr.begin[t], n = c - (tr.mode == MR_TOUR_TO_LAST ? 2u : 1u);
+    const uint32_t n_legs = tr.mode == MR_TOUR_OPEN ? n : n + 1u;
+    if (r >= n_legs)
+        return fail(MR_ERR_INVALID_ARG, "tour " + std::to_string(t) + ": leg " + std::to_string(r) + " is not below n_legs = " +
+                                            std::to_string(n_legs));
+    std::memset(res, 0, sizeof(*res));
+    if (rec.status == MR_ERR_LIMIT) {
+        res->status = MR_NOT_FOUND;
+        return MR_NOT_FOUND;
+    }
+    if (rec.status != MR_OK || rec.n_stops != n || rec.n_legs != n_legs) return fail(MR_ERR_DEVICE, "tour record is not its tour's");
+    // the cell of the tour's list a leg starts from and leads to
+    const auto at = [&](uint32_t k) -> uint32_t {  // k-th cell visited: the start, the stops in order, the end rule's
+        if (k == 0) return 0u;
+        if (k <= n) return 1u + rec.order[k - 1];
+        return tr.mode == MR_TOUR_TO_LAST ? c - 1u : 0u;
+    };
+    const uint32_t from = at(r), to = at(r + 1);
+    if (from >= c || to >= c) return fail(MR_ERR_DEVICE, "tour record names no stop");
+    return matrix_label_at(pl, tr.cells_h[tr.begin[t] + from], tr.cells_h[tr.begin[t] + to], res, cmds, cap);
+}
+
+extern "C" int mr_tour_num_points(const mr_plan *pl, uint32_t *n_points) {
+    if (!pl || !pl->tour) return fail(MR_ERR_INVALID_ARG, "not a tour plan");
+    if (!n_points) return fail(MR_ERR_INVALID_ARG, "null output");
+    *n_points = uint32_t(pl->mx.dst_v.size());
+    return MR_OK;
+}
+
+extern "C" double mr_tour_kernel_ms(const mr_plan *pl) { return pl && pl->tour ? pl->tour_ms : 0.0; }

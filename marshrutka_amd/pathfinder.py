@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = [
     "mr_nearest_plan_create", "mr_nearest_records", "mr_nearest_device_records", "mr_nearest_record_pitch",
     "mr_nearest_source_rows", "mr_nearest_label", "mr_grid_poi_cells",
     "mr_nearest_plan_create_ex", "mr_nearest_k", "mr_nearest_label_ex",
+    "mr_tour_plan_create", "mr_tour_records", "mr_tour_device_records", "mr_tour_leg_label", "mr_tour_num_points",
+    "mr_tour_kernel_ms",
 ]
 
 
@@ -193,6 +195,20 @@ def lib():
         L.mr_nearest_label_ex.restype = C.c_int
         L.mr_grid_poi_cells.argtypes = [vp, C.c_uint32, C.POINTER(mr_cell_index), C.c_uint32, C.POINTER(C.c_uint32)]
         L.mr_grid_poi_cells.restype = C.c_int
+        L.mr_tour_plan_create.argtypes = [vp, C.POINTER(mr_params), C.POINTER(mr_cell_index), C.POINTER(C.c_uint32),
+                                          C.c_uint32, C.c_uint32, C.POINTER(vp)]
+        L.mr_tour_plan_create.restype = C.c_int
+        L.mr_tour_records.argtypes = [vp, vp, C.c_uint64]
+        L.mr_tour_records.restype = C.c_int
+        L.mr_tour_device_records.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.mr_tour_device_records.restype = C.c_int
+        L.mr_tour_leg_label.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(mr_result), C.POINTER(mr_command),
+                                        C.c_uint32]
+        L.mr_tour_leg_label.restype = C.c_int
+        L.mr_tour_num_points.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.mr_tour_num_points.restype = C.c_int
+        L.mr_tour_kernel_ms.argtypes = [vp]
+        L.mr_tour_kernel_ms.restype = C.c_double
         _lib = L
     return _lib
 
@@ -399,6 +415,13 @@ class FindPath:
             plan.run()
             out[:, present] = plan.records()
         return out, dests
+
+    def eval_tours(self, tours: Sequence[Sequence[CellIndex]], mode: int = abi.TOUR_OPEN):
+        """The best visiting order of every tour after one pass of a TourPlan: its records()
+        (a structured array: legs, money, time_s, status, n_stops, n_legs, order, reserved)."""
+        plan = TourPlan(self.grid, self.params(), tours, mode)
+        plan.run()
+        return plan.records()
 
     def eval_batch_raw(self, pairs: Sequence[Tuple[CellIndex, CellIndex]]):
         n = len(pairs)
@@ -963,3 +986,91 @@ class NearestPlan(Plan):
 
     def fetch(self):
         raise NotImplementedError("nearest plans: use records() / label()")
+
+
+class TourPlan(Plan):
+    """Tours: run() finds, for every tour (a start cell, up to abi.TOUR_MAX_STOPS stops and the
+    plan's end rule `mode`), the order of the stops with the least summed leg metrics in the
+    parameters' order, ties to the lexicographically least sequence of stop positions
+    (mr_tour_plan_create).  `tours`: a sequence of cell sequences, each the start, the stops and,
+    under abi.TOUR_TO_LAST, the fixed end.  leg(t, r) rebuilds a leg's full TotalCost."""
+
+    def __init__(self, grid: MapGrid, params: Params, tours: Sequence[Sequence[CellIndex]], mode: int = abi.TOUR_OPEN):
+        self.grid = grid
+        self.tours = [list(t) for t in tours]
+        self.n = len(self.tours)
+        self.mode = mode
+        if not 0 <= int(mode) <= 0xFFFFFFFF:
+            raise EngineError(abi.MR_ERR_INVALID_ARG, "mode: an MR_TOUR_* value")
+        begin = [0]
+        for t in self.tours:
+            begin.append(begin[-1] + len(t))
+        self._p = params.to_c()
+        h = C.c_void_p()
+        st = lib().mr_tour_plan_create(grid.handle, C.byref(self._p), _cell_array([c for t in self.tours for c in t]),
+                                       (C.c_uint32 * len(begin))(*begin), self.n, int(mode), C.byref(h))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        self.handle = h
+
+    RECORD_DTYPE = [("legs", "<u4"), ("money", "<u4"), ("time_s", "<u4"), ("status", "<i4"), ("n_stops", "u1"),
+                    ("n_legs", "u1"), ("order", "u1", (abi.TOUR_MAX_STOPS,)), ("reserved", "<u4")]
+
+    def records(self):
+        """A structured array of n_tours mr_tour_record: legs, money, time_s (the winning order's
+        sums), status (MR_OK, or MR_ERR_LIMIT with zero sums for a tour the limit gate refused),
+        n_stops, n_legs, order (order[r] = the position of the r-th stop visited, 0xFF past
+        n_stops), reserved."""
+        import numpy as np
+        out = np.empty(max(self.n, 1), dtype=np.dtype(self.RECORD_DTYPE))
+        assert out.dtype.itemsize == C.sizeof(abi.mr_tour_record)
+        st = lib().mr_tour_records(self.handle, out.ctypes.data, self.n)
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return out[:self.n]
+
+    def orders(self) -> List[Optional[List[int]]]:
+        """Per tour the stop positions in visiting order, or None for a tour the limit gate refused."""
+        return [None if r["status"] != MR_OK else [int(x) for x in r["order"][:r["n_stops"]]] for r in self.records()]
+
+    def leg(self, t: int, r: int) -> Optional[TotalCost]:
+        """The full label of leg r of tour t's winning order; None for a tour the limit gate refused."""
+        res = mr_result()
+        cap = 64
+        while True:
+            cmds = (mr_command * cap)()
+            st = lib().mr_tour_leg_label(self.handle, t, r, C.byref(res), cmds, cap)
+            if st == MR_ERR_CAPACITY and res.n_commands > cap:
+                cap = res.n_commands
+                continue
+            break
+        if st == MR_NOT_FOUND:
+            return None
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        res.command_offset = 0
+        return result_from_c(res, cmds)
+
+    def device_records(self):
+        """(device pointer, bytes) of the records: n_tours rounded up to 4 records of 32 B."""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        st = lib().mr_tour_device_records(self.handle, C.byref(ptr), C.byref(n))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return ptr.value, n.value
+
+    @property
+    def num_points(self) -> int:
+        """The distinct cells of all tours: the side of the plan's internal matrix."""
+        out = C.c_uint32()
+        st = lib().mr_tour_num_points(self.handle, C.byref(out))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return out.value
+
+    def tour_ms(self) -> float:
+        """Average time of a pass's tour launches over the window the last kernel_ms() closed."""
+        return lib().mr_tour_kernel_ms(self.handle)
+
+    def fetch(self):
+        raise NotImplementedError("tour plans: use records() / leg()")
