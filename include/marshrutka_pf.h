@@ -606,6 +606,59 @@ int mr_tour_num_points(const mr_plan *plan, uint32_t *n_points);
  * mr_plan_fill_ms); mr_plan_kernel_ms itself gives the matrix read-off's.  0 for any other plan */
 double mr_tour_kernel_ms(const mr_plan *plan);
 
+/* ---- nearest source: the best (or worst) listed source per destination ---- */
+/* The other axis of a nearest plan: for caller destination j and group g of sources, the source
+ * i of the group (group_of_src[i] == g; NULL puts every source in group 0) whose
+ * m = metrics of FindPath::eval(sources[i], dests[j]) has the least (MR_SRC_BEST) or the greatest
+ * (MR_SRC_WORST) (m[q0], m[q1], m[q2]), (q0, q1, q2) the parameters' metric order completed as
+ * nearest plans complete it.  In both modes ties on all three metrics go to the smallest i.
+ * Routes are directed, so this is not a nearest plan with the lists swapped.  A source equal to
+ * the destination takes part with the matrix record {0, 0, 0, 0xFFFFFFFF}.  Cells may repeat in
+ * both lists.  The record's first four words are the matrix record of (winner, j), word for
+ * word; an empty group reads src = 0xFFFFFFFF and every other word 0.
+ * The plan owns a matrix plan's state over the two lists (distinct sources x n_dst rounded up to
+ * 8 records of 16 B on the device); mr_plan_run enqueues the matrix pass and then the reduction's
+ * launches.  mr_plan_run / _wait / _get_stats / _kernel_ms / _destroy apply.
+ * Errors, all argument checks before any device is touched (mr_last_error names the position):
+ * MR_ERR_INVALID_ARG for a null pointer (group_of_src may be null), n_src, n_dst or n_groups
+ * == 0, n_groups > n_src, a group id >= n_groups, which > 1; MR_ERR_INVALID_INDEX for a source
+ * or destination that is not a grid cell; MR_ERR_LIMIT when the matrix block, the records or the
+ * partial records of split groups exceed the device block cache's largest block (16 GiB);
+ * MR_ERR_NO_DEVICE as for the other plans.  Every other plan kind's accessors return
+ * MR_ERR_INVALID_ARG on this plan, the mr_nearest_src_* accessors on any other plan.
+ * MR_ERR_LIMIT for labels holds as stated at mr_status: the accessors that wait report it. */
+enum { MR_SRC_BEST = 0, MR_SRC_WORST = 1 };
+typedef struct mr_nearest_src_record {
+    uint32_t legs, money, time_s, via; /* the matrix record of (winner, destination) */
+    uint32_t src;                      /* the winner's position in sources[]; 0xFFFFFFFF: empty group */
+    uint32_t reserved[3];              /* 0 */
+} mr_nearest_src_record;               /* 32 B: four a 128 B line */
+int mr_nearest_src_plan_create(const mr_grid *grid, const mr_params *params, const mr_cell_index *sources, uint32_t n_src,
+                               const uint32_t *group_of_src /* n_src group ids, or NULL */, uint32_t n_groups,
+                               const mr_cell_index *dests, uint32_t n_dst, uint32_t which, mr_plan **out);
+/* the record of (destination j, group g) at out[j * n_groups + g] (waits); MR_ERR_CAPACITY if
+ * cap_records < n_dst * n_groups */
+int mr_nearest_src_records(mr_plan *plan, mr_nearest_src_record *out, uint64_t cap_records);
+/* device records: [group][pitch] mr_nearest_src_record, pitch = n_dst rounded up to 4, the
+ * destinations in the caller's order, pad records zeros.  Waits for the passes enqueued so far;
+ * the next mr_plan_run rewrites them */
+int mr_nearest_src_device_records(mr_plan *plan, void **d_records, uint64_t *bytes);
+int mr_nearest_src_record_pitch(mr_plan *plan, uint32_t *records_per_group);
+/* the winner of (j, g) rebuilt in full, as mr_matrix_label rebuilds a pair: MR_OK,
+ * MR_ERR_CAPACITY (out->n_commands > cap), MR_NOT_FOUND for an empty group, MR_ERR_INVALID_ARG
+ * for j >= n_dst or g >= n_groups */
+int mr_nearest_src_label(mr_plan *plan, uint32_t j, uint32_t g, mr_result *out, mr_command *cmds, uint32_t cap);
+/* how the plan cut its groups: the segment length in sources, the groups reduced in one segment,
+ * the groups split into several (merged by a second launch), and the non-empty groups whose size
+ * is a multiple of the segment length.  Any output may be null.  A diagnostic for tests and
+ * tuning, with no stability promise: what it reports follows the host's segmentation, which may
+ * change without an ABI version; do not build on it */
+int mr_nearest_src_segmentation(const mr_plan *plan, uint32_t *seg_len, uint32_t *groups_whole, uint32_t *groups_split,
+                                uint32_t *groups_on_edge);
+/* the reduction launches' time a pass, averaged over the window the last mr_plan_kernel_ms closed
+ * (as mr_tour_kernel_ms).  0 for any other plan */
+double mr_nearest_src_kernel_ms(const mr_plan *plan);
+
 /* ---- misc ---------------------------------------------------------------- */
 uint32_t mr_abi_version(void);
 /* Human-readable description of the last error on this thread. */

@@ -181,6 +181,23 @@ pub const MR_TOUR_OPEN: u32 = 0;
 pub const MR_TOUR_RETURN: u32 = 1;
 pub const MR_TOUR_TO_LAST: u32 = 2;
 
+/// A nearest-source plan's record: the matrix record of (winner, destination) and `src`, the
+/// winner's position in the caller's sources (0xFFFFFFFF, all other words 0: an empty group).
+#[repr(C)]
+#[derive(Copy, Clone, Default, Debug)]
+pub struct mr_nearest_src_record {
+    pub legs: u32,
+    pub money: u32,
+    pub time_s: u32,
+    pub via: u32,
+    pub src: u32,
+    pub reserved: [u32; 3],
+}
+
+/// Which source of a group a nearest-source plan keeps (`which` of `mr_nearest_src_plan_create`).
+pub const MR_SRC_BEST: u32 = 0;
+pub const MR_SRC_WORST: u32 = 1;
+
 /// Opaque handles.
 pub enum mr_grid {}
 pub enum mr_plan {}
@@ -295,6 +312,19 @@ extern "C" {
                              cap: u32) -> c_int;
     pub fn mr_tour_num_points(plan: *const mr_plan, n_points: *mut u32) -> c_int;
     pub fn mr_tour_kernel_ms(plan: *const mr_plan) -> f64;
+    // nearest source: per destination and group of sources the best (or worst) listed source;
+    // group_of_src may be null (one group); the record of (j, g) lands at out[j * n_groups + g]
+    pub fn mr_nearest_src_plan_create(grid: *const mr_grid, params: *const mr_params, sources: *const mr_cell_index,
+                                      n_src: u32, group_of_src: *const u32, n_groups: u32, dests: *const mr_cell_index,
+                                      n_dst: u32, which: u32, out: *mut *mut mr_plan) -> c_int;
+    pub fn mr_nearest_src_records(plan: *mut mr_plan, out: *mut mr_nearest_src_record, cap_records: u64) -> c_int;
+    pub fn mr_nearest_src_device_records(plan: *mut mr_plan, d_records: *mut *mut c_void, bytes: *mut u64) -> c_int;
+    pub fn mr_nearest_src_record_pitch(plan: *mut mr_plan, records_per_group: *mut u32) -> c_int;
+    pub fn mr_nearest_src_label(plan: *mut mr_plan, j: u32, g: u32, out: *mut mr_result, cmds: *mut mr_command,
+                                cap: u32) -> c_int;
+    pub fn mr_nearest_src_segmentation(plan: *const mr_plan, seg_len: *mut u32, groups_whole: *mut u32,
+                                       groups_split: *mut u32, groups_on_edge: *mut u32) -> c_int;
+    pub fn mr_nearest_src_kernel_ms(plan: *const mr_plan) -> f64;
 
     // misc
     pub fn mr_abi_version() -> u32;

@@ -101,6 +101,15 @@ class mr_tour_record(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+SRC_BEST, SRC_WORST = 0, 1  # MR_SRC_*: which source of a group a nearest-source plan keeps
+SRC_NONE = 0xFFFFFFFF       # mr_nearest_src_record.src of an empty group
+
+
+class mr_nearest_src_record(C.Structure):
+    _fields_ = [("legs", C.c_uint32), ("money", C.c_uint32), ("time_s", C.c_uint32), ("via", C.c_uint32),
+                ("src", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 assert C.sizeof(mr_cell_index) == 8
 assert C.sizeof(mr_cell) == 16
 assert C.sizeof(mr_command) == 40
@@ -108,6 +117,7 @@ assert C.sizeof(mr_result) == 32
 assert C.sizeof(mr_query) == 16
 assert C.sizeof(mr_nearest_record) == 32
 assert C.sizeof(mr_tour_record) == 32
+assert C.sizeof(mr_nearest_src_record) == 32
 
 
 # ---- value types -------------------------------------------------------------

@@ -14,9 +14,9 @@ LIB_PATH = os.path.join(LIB_DIR, "libmarshrutka_pf.so")
 # compiled in parallel and linked into one shared library
 SOURCES = ["mr_k_region.hip", "mr_k_groupq.hip", "mr_k_group.hip", "mr_k_group_nl.hip", "mr_k_lane.hip", "mr_k_lane_memo.hip", "mr_k_lane24.hip", "mr_k_lane32.hip", "mr_k_lane_nl.hip", "mr_k_lane_nl2.hip", "mr_k_wide2.hip", "mr_k_wide5.hip", "mr_k_wide8.hip", "mr_k_hub_lin.hip", "mr_k_hub_nl.hip",
            "mr_k_hub.hip", "mr_k_wide.hip",
-           "mr_k_solve.hip", "mr_k_fill.hip", "mr_k_matrix.hip", "mr_k_nearest.hip", "mr_k_knearest.hip", "mr_k_tour.hip", "mr_k_cert.hip", "mr_k_decode.hip",
+           "mr_k_solve.hip", "mr_k_fill.hip", "mr_k_matrix.hip", "mr_k_nearest.hip", "mr_k_knearest.hip", "mr_k_tour.hip", "mr_k_nearest_src.hip", "mr_k_cert.hip", "mr_k_decode.hip",
            "mr_host.cpp", "mr_html.cpp", "mr_render.cpp"]
-HEADERS = ["mr_engine.hpp", "mr_label.hpp", "mr_pool.hpp", "mr_devmem.hpp", "mr_device.hpp", "mr_matrix.hpp", "mr_nearest.hpp", "mr_knearest.hpp", "mr_tour.hpp", "mr_hub_lane.hpp", "mr_hub_group.hpp", "mr_cert.hpp", "mr_cert_tile.hpp", os.path.join("..", "..", "include", "marshrutka_pf.h")]
+HEADERS = ["mr_engine.hpp", "mr_label.hpp", "mr_pool.hpp", "mr_devmem.hpp", "mr_device.hpp", "mr_matrix.hpp", "mr_nearest.hpp", "mr_knearest.hpp", "mr_tour.hpp", "mr_nearest_src.hpp", "mr_hub_lane.hpp", "mr_hub_group.hpp", "mr_cert.hpp", "mr_cert_tile.hpp", os.path.join("..", "..", "include", "marshrutka_pf.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
          "-Wno-unused-result", "-munsafe-fp-atomics"]

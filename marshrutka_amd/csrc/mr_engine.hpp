@@ -281,6 +281,25 @@ struct TourArgs {
     uint4 *records;
     uint32_t pitch, mode, first, count, nmax;
 };
+// Nearest-source plans (DESIGN.md section 3b'''''): the argument block of nearest_src_kernel and
+// nearest_src_merge_kernel, passed by value.  rows: the plan's matrix rows ([plan source][mx_pitch]
+// records of 16 B, the columns the caller's destinations in order), written by the matrix pass
+// before these launches on the stream.  The sources are stable-sorted by group: row_of[k] is
+// sorted source k's matrix row (followed by 16 spare entries of row 0), pos_of[k] its caller position.  segs[s] = {first sorted source,
+// sources, group, slab of the partials or kNone32 where the segment is its whole group and stores
+// the final record}; an item is a (segment, 64-destination chunk).  splits[m] = {group, first
+// slab, slabs, 0} for the groups of more than one segment.  records: [group][pitch], partials:
+// [slab][pitch], two uint4 a record (mr_nearest_src_record), pitch = n_dst rounded up to 4.
+struct NearestSrcArgs {
+    const uint4 *rows;
+    const uint32_t *row_of;
+    const uint32_t *pos_of;
+    const uint4 *segs;
+    const uint4 *splits;
+    uint4 *records;
+    uint4 *partials;
+    uint32_t mx_pitch, pitch, n_dst, n_chunk, n_seg, n_split;
+};
 // KArgs::all_mode: a cell word per (source, cell), a record per (source, listed destination),
 // or a record per (source, group of listed destinations)
 constexpr uint32_t kAllCells = 1u, kAllMatrix = 2u, kAllNearest = 3u;

@@ -46,6 +46,10 @@ int knearest_blocks_per_cu(const uint32_t perm[3]);
 uint32_t tour_lds_bytes(uint32_t nmax, bool wave);
 hipError_t launch_tour(const TourArgs &ta, const uint32_t perm[3], bool wave, uint32_t gx, hipStream_t stream);
 int tour_blocks_per_cu(const uint32_t perm[3], bool wave, uint32_t nmax);
+hipError_t launch_nearest_src(const NearestSrcArgs &na, const uint32_t perm[3], bool worst, uint32_t gx, hipStream_t stream);
+hipError_t launch_nearest_src_merge(const NearestSrcArgs &na, const uint32_t perm[3], bool worst, hipStream_t stream);
+int nearest_src_blocks_per_cu(const uint32_t perm[3], bool worst);
+uint32_t nearest_src_waves_per_block();
 hipError_t launch_hub_fill(const KArgs *hub_args, const KArgs *fill_args, const uint32_t perm[3], uint32_t spw,
                            uint32_t hub_blocks, uint32_t fill_blocks, uint32_t lds_bytes, hipStream_t stream);
 int hub_fill_blocks_per_cu(const uint32_t perm[3], uint32_t spw, uint32_t lds_bytes);
@@ -1607,6 +1611,10 @@ struct mr_plan {
     // a tour plan: a matrix plan over the tours' distinct cells (matrix is set too), reduced on
     // the device to one record a tour by the tour launches that follow each pass (Tour below)
     bool tour = false;
+    // a nearest-source plan: a matrix plan over the caller's lists (matrix is set too), reduced
+    // on the device over each destination's sources by the launches that follow each pass
+    // (NearestSrc below)
+    bool nsrc = false;
     bool grid_in_lds = false;
     uint32_t algo = kAlgoGeneric;
     uint32_t blocks = 0, cus = 256;
@@ -1614,7 +1622,8 @@ struct mr_plan {
     bool fb_none = false;                 // a completed pass of this plan had no fallback sources
     uint32_t runs = 0;
     double fill_ms = 0.0;                 // all-destinations: average fill launch of the last window
-    double tour_ms = 0.0;                 // tour plans: average of a pass's tour launches, the last window
+    // tour and nearest-source plans: average of a pass's reduction launches, the last window
+    double tour_ms = 0.0;
 
     Stream stream;      // the plan's own
     Stream hub_stream;  // overlap on two streams: the specials' solves of every slot
@@ -1637,7 +1646,7 @@ struct mr_plan {
     // must not pile up events: mr_plan_run folds the oldest beyond kMaxTimed)
     double acc_ms = 0.0, acc_fill_ms = 0.0, acc_tour_ms = 0.0;
     uint32_t acc_n = 0, acc_fill_n = 0, acc_tour_n = 0;
-    // tour plans: the event pair round each pass's tour launches.  A hub pass's fill pair ends
+    // tour and nearest-source plans: the event pair round each pass's reduction launches.  A hub pass's fill pair ends
     // at `first` (the matrix read-off's time stays its own), so these are folded after
     // timed_fill, and no more of them
     std::vector<TimedPass> timed_tour;
@@ -1714,6 +1723,18 @@ struct mr_plan {
         };
         std::vector<Launch> launches;
     } tr;
+    // nearest-source plans: the sources stable-sorted by group (row_of: their matrix rows, pos_of:
+    // their caller positions), the segments and the split groups (NearestSrcArgs), the records
+    // [group][pitch] (zeroed once: the pad records stay zeros) and the split groups' partials
+    struct NearestSrc {
+        DevBuf<uint32_t> row_of, pos_of;
+        DevBuf<uint4> segs, splits, records, partials;
+        NearestSrcArgs args{};
+        uint32_t n_groups = 0, which = 0, gx = 1;
+        // the segmentation, for mr_nearest_src_segmentation: the segment length, and the groups
+        // of one segment, of several, and of a size that is a positive multiple of the length
+        uint32_t seg_len = 0, whole = 0, split = 0, on_edge = 0;
+    } ns;
     struct Hub {
         uint32_t n_lane = 0;               // sources on the lane kernel; the rest on hub_kernel
         uint32_t lane_g = 0;               // > 0: the n_lane sources run G lanes each (hub_group_kernel)
@@ -3127,6 +3148,21 @@ static hipError_t run_tours(mr_plan *pl, hipStream_t s) {
     return e;
 }
 
+// a nearest-source plan's launches behind its matrix pass: the reduction and, where a group was
+// split, the merge; timed as the tour launches are
+static hipError_t run_nearest_src(mr_plan *pl, hipStream_t s) {
+    Event t0, t1;
+    if (t0.create() != hipSuccess || t1.create() != hipSuccess) return hipErrorUnknown;
+    (void)hipEventRecord(t0.get(), s);
+    if (!pl->timed_fill.empty() && !pl->timed_fill.back().second) pl->timed_fill.back().second = t0.get();
+    const mr_plan::NearestSrc &ns = pl->ns;
+    hipError_t e = launch_nearest_src(ns.args, pl->ka.p.perm, ns.which == MR_SRC_WORST, ns.gx, s);
+    if (e == hipSuccess && ns.args.n_split) e = launch_nearest_src_merge(ns.args, pl->ka.p.perm, ns.which == MR_SRC_WORST, s);
+    (void)hipEventRecord(t1.get(), s);
+    pl->timed_tour.push_back({std::move(t0), std::move(t1)});
+    return e;
+}
+
 extern "C" int mr_plan_run(mr_plan *pl, void *stream) {
     if (!pl) return fail(MR_ERR_INVALID_ARG, "null plan");
     hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : pl->stream.get();
@@ -3164,6 +3200,7 @@ extern "C" int mr_plan_run(mr_plan *pl, void *stream) {
     if (e == hipSuccess && pl->out.ovf_order && !pl->all_mode)
         e = launch_ovf_order(pl->cur().args.get(), nrec_of(pl->hp), pl->out.ovf_tmp.get(), s);
     if (e == hipSuccess && pl->tour) e = run_tours(pl, s);
+    if (e == hipSuccess && pl->nsrc) e = run_nearest_src(pl, s);
     (void)hipEventRecord(e1.get(), s);
     // the pass's end event doubles as the plan's last event (plan_sync): a record of
     // its own cost ~6 us of command-processor time per pass.  `timed` owns it from here.
@@ -4417,7 +4454,7 @@ extern "C" int mr_matrix_plan_create(const mr_grid *g, const mr_params *prm, con
 
 // a matrix plan whose last pass raised no device error (waits for the plan)
 static int matrix_plan(mr_plan *pl) {
-    if (!pl || !pl->matrix || pl->nearest || pl->tour) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest || pl->tour || pl->nsrc) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     uint32_t flags = 0;
     return check_device_errors(pl, flags);
 }
@@ -4446,7 +4483,7 @@ extern "C" int mr_matrix_records(mr_plan *pl, mr_label_record *out, uint64_t cap
 }
 
 extern "C" int mr_matrix_device_records(mr_plan *pl, void **d_records, uint64_t *bytes) {
-    if (!pl || !pl->matrix || pl->nearest || pl->tour) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest || pl->tour || pl->nsrc) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // whole records behind the pointer
     if (d_records) *d_records = pl->mx.rows.get();
     if (bytes) *bytes = uint64_t(pl->ka.nsrc) * pl->mx.pitch * sizeof(mr_label_record);
@@ -4454,14 +4491,14 @@ extern "C" int mr_matrix_device_records(mr_plan *pl, void **d_records, uint64_t 
 }
 
 extern "C" int mr_matrix_record_pitch(mr_plan *pl, uint32_t *records_per_row) {
-    if (!pl || !pl->matrix || pl->nearest || pl->tour) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest || pl->tour || pl->nsrc) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     if (!records_per_row) return fail(MR_ERR_INVALID_ARG, "null output");
     *records_per_row = pl->mx.pitch;
     return MR_OK;
 }
 
 extern "C" int mr_matrix_source_rows(const mr_plan *pl, uint32_t *row_of_source, uint32_t n_src) {
-    if (!pl || !pl->matrix || pl->nearest || pl->tour) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
+    if (!pl || !pl->matrix || pl->nearest || pl->tour || pl->nsrc) return fail(MR_ERR_INVALID_ARG, "not a matrix plan");
     if (n_src && !row_of_source) return fail(MR_ERR_INVALID_ARG, "null output");
     for (uint32_t i = 0; i < n_src; ++i) row_of_source[i] = i < pl->src_of_input.size() ? pl->src_of_input[i] : kNone32;
     return MR_OK;
@@ -4858,3 +4895,214 @@ extern "C" int mr_tour_num_points(const mr_plan *pl, uint32_t *n_points) {
 }
 
 extern "C" double mr_tour_kernel_ms(const mr_plan *pl) { return pl && pl->tour ? pl->tour_ms : 0.0; }
+
+// ------------------------------------------------------------ nearest source
+// The floor of the segment length L where the host cuts groups (plan_nearest_src); it bounds L,
+// not a cut group's last segment, which is the remainder.  A segment of L
+// sources is L / 8 rounds of loads in its wave, and every segment of a group is one more slab the
+// merge's lane folds, 8 slabs a round, so both ends are chains of memory latencies: a group of n
+// sources costs about L / 8 + n / (8 L) rounds.  Chosen on 65 536 sources x 64 destinations in 4
+// groups, where 32, 64, 128 and 256 were measured and 128 was the fastest (DESIGN.md section
+// 3b''''').
+static constexpr uint32_t kNsrcSegFloor = 128;
+
+// the nearest-source state of a matrix plan over the caller's lists: the sources by group, the
+// segments, the records and the partials, and the reduction's grid
+static int plan_nearest_src(mr_plan *pl, const std::vector<uint32_t> &group, uint32_t n_groups, uint32_t which) {
+    mr_plan::NearestSrc &ns = pl->ns;
+    const uint32_t n_src = pl->mx.n_src, n_dst = pl->mx.n_dst;
+    ns.n_groups = n_groups;
+    ns.which = which;
+    std::vector<uint32_t> pos(n_src), row(n_src), gfirst(size_t(n_groups) + 1, 0u);
+    for (uint32_t i = 0; i < n_src; ++i) pos[i] = i, ++gfirst[group[i] + 1];
+    for (uint32_t g = 0; g < n_groups; ++g) gfirst[g + 1] += gfirst[g];
+    std::stable_sort(pos.begin(), pos.end(), [&](uint32_t x, uint32_t y) { return group[x] < group[y]; });
+    for (uint32_t k = 0; k < n_src; ++k) row[k] = pl->src_of_input[pos[k]];
+    row.resize(size_t(n_src) + 16, 0u);  // the kernel prefetches two rounds of 8 row indices past a segment's end
+    uint32_t largest = 1;
+    for (uint32_t g = 0; g < n_groups; ++g) largest = std::max(largest, gfirst[g + 1] - gfirst[g]);
+    const int per_cu = nearest_src_blocks_per_cu(pl->ka.p.perm, which == MR_SRC_WORST);
+    if (per_cu <= 0) return fail(MR_ERR_DEVICE, "nearest-source kernel: no workgroup fits a CU");
+    // groups are cut only where the chunks x groups alone leave resident wave slots empty, into
+    // as many segments as fill them, none shorter than the floor
+    const uint64_t pitch = (uint64_t(n_dst) + 3) / 4 * 4, n_chunk = (uint64_t(n_dst) + 63) / 64;
+    const uint64_t wpb = nearest_src_waves_per_block();
+    const uint64_t slots = uint64_t(per_cu) * pl->cus * wpb, whole = n_chunk * n_groups;
+    uint32_t seg = largest;
+    if (whole < slots) seg = std::max<uint32_t>(kNsrcSegFloor, uint32_t((largest + (slots + whole - 1) / whole - 1) / ((slots + whole - 1) / whole)));
+    if (const char *e = std::getenv("MR_NSRC_SEG")) seg = uint32_t(std::max(1, std::atoi(e)));
+    ns.seg_len = seg;
+    std::vector<uint4> segs, splits;
+    uint64_t slabs = 0;
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        const uint32_t first = gfirst[g], size = gfirst[g + 1] - first, z = std::max(1u, (size + seg - 1) / seg);
+        if (size && size % seg == 0) ++ns.on_edge;
+        if (z == 1) {
+            ++ns.whole;
+            segs.push_back(make_uint4(first, size, g, kNone32));  // (an empty group: a segment of no source)
+            continue;
+        }
+        ++ns.split;
+        splits.push_back(make_uint4(g, uint32_t(slabs), z, 0u));
+        for (uint32_t i = 0; i < z; ++i, ++slabs)
+            segs.push_back(make_uint4(first + i * seg, std::min(seg, size - i * seg), g, uint32_t(slabs)));
+    }
+    const uint64_t cap = kMatrixMaxBytes / sizeof(mr_nearest_src_record);
+    if (n_groups * pitch > cap)
+        return fail(MR_ERR_LIMIT, "nearest-source plan: " + std::to_string(n_groups) + " groups x " + std::to_string(pitch) +
+                                      " records of 32 B exceed the device block cache's largest block");
+    if (slabs * pitch > cap || segs.size() * n_chunk > 0xFFFFFFFFull)
+        return fail(MR_ERR_LIMIT, "nearest-source plan: " + std::to_string(slabs) + " segments x " + std::to_string(pitch) +
+                                      " partial records of 32 B exceed the device block cache's largest block");
+    if (upload(ns.row_of, row) != hipSuccess || upload(ns.pos_of, pos) != hipSuccess || upload(ns.segs, segs) != hipSuccess ||
+        upload(ns.splits, splits) != hipSuccess || ns.records.alloc_zero(size_t(n_groups * pitch * 2)) != hipSuccess ||
+        ns.partials.alloc(size_t(std::max<uint64_t>(slabs * pitch * 2, 1))) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "hipMalloc nearest-source tables");
+    NearestSrcArgs &a = ns.args;
+    a.rows = pl->mx.rows.get();
+    a.row_of = ns.row_of.get();
+    a.pos_of = ns.pos_of.get();
+    a.segs = ns.segs.get();
+    a.splits = ns.splits.get();
+    a.records = ns.records.get();
+    a.partials = ns.partials.get();
+    a.mx_pitch = pl->mx.pitch;
+    a.pitch = uint32_t(pitch);
+    a.n_dst = n_dst;
+    a.n_chunk = uint32_t(n_chunk);
+    a.n_seg = uint32_t(segs.size());
+    a.n_split = uint32_t(splits.size());
+    ns.gx = resident_grid((segs.size() * n_chunk + wpb - 1) / wpb, uint64_t(per_cu) * pl->cus);
+    if (const char *e = std::getenv("MR_NSRC_GX")) ns.gx = uint32_t(std::max(1, std::atoi(e)));
+    return MR_OK;
+}
+
+extern "C" int mr_nearest_src_plan_create(const mr_grid *g, const mr_params *prm, const mr_cell_index *sources, uint32_t n_src,
+                                          const uint32_t *group_of_src, uint32_t n_groups, const mr_cell_index *dests,
+                                          uint32_t n_dst, uint32_t which, mr_plan **out) {
+    if (!g || !prm || !out || !sources || !dests) return fail(MR_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!n_src || !n_dst || !n_groups)
+        return fail(MR_ERR_INVALID_ARG, "a nearest-source plan needs at least one source, one destination and one group");
+    if (n_groups > n_src)
+        return fail(MR_ERR_INVALID_ARG, "n_groups " + std::to_string(n_groups) + " is more than the " + std::to_string(n_src) + " sources");
+    if (which > MR_SRC_WORST) return fail(MR_ERR_INVALID_ARG, "which " + std::to_string(which) + " is not an MR_SRC_* value");
+    std::vector<uint32_t> group(n_src, 0u);
+    for (uint32_t i = 0; group_of_src && i < n_src; ++i) {
+        if (group_of_src[i] >= n_groups)
+            return fail(MR_ERR_INVALID_ARG, "source " + std::to_string(i) + ": group " + std::to_string(group_of_src[i]) +
+                                                " is not below n_groups = " + std::to_string(n_groups));
+        group[i] = group_of_src[i];
+    }
+    std::vector<uint32_t> sv(n_src), dv(n_dst);
+    for (uint32_t i = 0; i < n_src; ++i)
+        if (!g->find(sources[i], sv[i])) return fail(MR_ERR_INVALID_INDEX, "source " + std::to_string(i) + " is not a grid cell");
+    for (uint32_t j = 0; j < n_dst; ++j)
+        if (!g->find(dests[j], dv[j]))
+            return fail(MR_ERR_INVALID_INDEX, "destination " + std::to_string(j) + " is not a grid cell");
+    // the limits that need no device: the matrix block (a row a distinct source) and the records;
+    // the partials' follows the segmentation (plan_nearest_src)
+    std::sort(sv.begin(), sv.end());
+    const uint64_t rows = uint64_t(std::unique(sv.begin(), sv.end()) - sv.begin());
+    if (rows * ((uint64_t(n_dst) + 7) / 8 * 8) > kMatrixMaxBytes / sizeof(mr_label_record))
+        return fail(MR_ERR_LIMIT, "nearest-source plan: the matrix of " + std::to_string(rows) + " distinct sources x " +
+                                      std::to_string(n_dst) + " destinations exceeds the device block cache's largest block");
+    if (uint64_t(n_groups) * ((uint64_t(n_dst) + 3) / 4 * 4) > kMatrixMaxBytes / sizeof(mr_nearest_src_record))
+        return fail(MR_ERR_LIMIT, "nearest-source plan: " + std::to_string(n_groups) + " groups x " + std::to_string(n_dst) +
+                                      " records of 32 B exceed the device block cache's largest block");
+    if (!mr_device_available()) return fail(MR_ERR_NO_DEVICE, "no gfx950 device visible (no CPU fallback)");
+    std::vector<mr_query> qs(n_src);
+    for (uint32_t i = 0; i < n_src; ++i) qs[i].from = qs[i].to = sources[i];
+    int st = plan_create(g, prm, qs.data(), n_src, 16, out, true, &dv);
+    if (st != MR_OK) return st;
+    mr_plan *pl = *out;
+    pl->mx.n_src = n_src;
+    pl->nsrc = true;
+    if ((st = plan_nearest_src(pl, group, n_groups, which)) != MR_OK) {
+        const std::string msg = mr_last_error();
+        mr_plan_destroy(pl);
+        *out = nullptr;
+        return fail(st, msg);
+    }
+    return MR_OK;
+}
+
+// a nearest-source plan whose last pass raised no device error (waits for the plan)
+static int nearest_src_plan(mr_plan *pl) {
+    if (!pl || !pl->nsrc) return fail(MR_ERR_INVALID_ARG, "not a nearest-source plan");
+    uint32_t flags = 0;
+    return check_device_errors(pl, flags);
+}
+
+extern "C" int mr_nearest_src_records(mr_plan *pl, mr_nearest_src_record *out, uint64_t cap_records) {
+    if (int st = nearest_src_plan(pl)) return st;
+    if (!out) return fail(MR_ERR_INVALID_ARG, "null output");
+    const mr_plan::NearestSrc &ns = pl->ns;
+    const uint64_t n_dst = pl->mx.n_dst, ng = ns.n_groups;
+    if (cap_records < n_dst * ng) return fail(MR_ERR_CAPACITY, "mr_nearest_src_records: output shorter than n_dst x n_groups");
+    const mr_nearest_src_record *recs = reinterpret_cast<const mr_nearest_src_record *>(ns.records.get());
+    // the device holds [group][pitch], the caller gets [destination][group]: one group is one
+    // copy as it stands; more groups come over whole, up to 64 MiB of them a copy, and are
+    // transposed on the host
+    if (ng == 1) {
+        if (hipMemcpy(out, recs, size_t(n_dst) * sizeof(*out), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(MR_ERR_DEVICE, "copy nearest-source records");
+        return MR_OK;
+    }
+    const uint64_t pitch = ns.args.pitch;
+    const uint64_t step = std::max<uint64_t>(1, (uint64_t(64) << 20) / (pitch * sizeof(*out)));
+    std::vector<mr_nearest_src_record> block(size_t(std::min(step, ng) * pitch));
+    for (uint64_t g0 = 0; g0 < ng; g0 += step) {
+        const uint64_t n = std::min(step, ng - g0);
+        if (hipMemcpy(block.data(), recs + g0 * pitch, size_t(n * pitch) * sizeof(*out), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(MR_ERR_DEVICE, "copy nearest-source records");
+        for (uint64_t j = 0; j < n_dst; ++j)
+            for (uint64_t g = 0; g < n; ++g) out[j * ng + g0 + g] = block[g * pitch + j];
+    }
+    return MR_OK;
+}
+
+extern "C" int mr_nearest_src_device_records(mr_plan *pl, void **d_records, uint64_t *bytes) {
+    if (!pl || !pl->nsrc) return fail(MR_ERR_INVALID_ARG, "not a nearest-source plan");
+    if (!plan_sync(pl)) return fail(MR_ERR_DEVICE, "sync");  // whole records behind the pointer
+    if (d_records) *d_records = pl->ns.records.get();
+    if (bytes) *bytes = uint64_t(pl->ns.n_groups) * pl->ns.args.pitch * sizeof(mr_nearest_src_record);
+    return MR_OK;
+}
+
+extern "C" int mr_nearest_src_record_pitch(mr_plan *pl, uint32_t *records_per_group) {
+    if (!pl || !pl->nsrc) return fail(MR_ERR_INVALID_ARG, "not a nearest-source plan");
+    if (!records_per_group) return fail(MR_ERR_INVALID_ARG, "null output");
+    *records_per_group = pl->ns.args.pitch;
+    return MR_OK;
+}
+
+extern "C" int mr_nearest_src_label(mr_plan *pl, uint32_t j, uint32_t g, mr_result *res, mr_command *cmds, uint32_t cap) {
+    if (int st = nearest_src_plan(pl)) return st;
+    if (!res) return fail(MR_ERR_INVALID_ARG, "null result");
+    const mr_plan::NearestSrc &ns = pl->ns;
+    if (j >= pl->mx.n_dst || g >= ns.n_groups) return fail(MR_ERR_INVALID_ARG, "nearest-source index");
+    mr_nearest_src_record rec;
+    if (hipMemcpy(&rec, reinterpret_cast<const mr_nearest_src_record *>(ns.records.get()) + size_t(g) * ns.args.pitch + j, sizeof(rec),
+                  hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(MR_ERR_DEVICE, "copy nearest-source record");
+    std::memset(res, 0, sizeof(*res));
+    if (rec.src == kNone32) {
+        res->status = MR_NOT_FOUND;
+        return MR_NOT_FOUND;
+    }
+    if (rec.src >= pl->mx.n_src) return fail(MR_ERR_DEVICE, "nearest-source record names no source");
+    return matrix_label_at(pl, rec.src, j, res, cmds, cap);
+}
+
+extern "C" int mr_nearest_src_segmentation(const mr_plan *pl, uint32_t *seg_len, uint32_t *groups_whole, uint32_t *groups_split,
+                                           uint32_t *groups_on_edge) {
+    if (!pl || !pl->nsrc) return fail(MR_ERR_INVALID_ARG, "not a nearest-source plan");
+    if (seg_len) *seg_len = pl->ns.seg_len;
+    if (groups_whole) *groups_whole = pl->ns.whole;
+    if (groups_split) *groups_split = pl->ns.split;
+    if (groups_on_edge) *groups_on_edge = pl->ns.on_edge;
+    return MR_OK;
+}
+
+extern "C" double mr_nearest_src_kernel_ms(const mr_plan *pl) { return pl && pl->nsrc ? pl->tour_ms : 0.0; }

@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = [
     "mr_nearest_plan_create_ex", "mr_nearest_k", "mr_nearest_label_ex",
     "mr_tour_plan_create", "mr_tour_records", "mr_tour_device_records", "mr_tour_leg_label", "mr_tour_num_points",
     "mr_tour_kernel_ms",
+    "mr_nearest_src_plan_create", "mr_nearest_src_records", "mr_nearest_src_device_records",
+    "mr_nearest_src_record_pitch", "mr_nearest_src_label", "mr_nearest_src_segmentation", "mr_nearest_src_kernel_ms",
 ]
 
 
@@ -209,6 +211,23 @@ def lib():
         L.mr_tour_num_points.restype = C.c_int
         L.mr_tour_kernel_ms.argtypes = [vp]
         L.mr_tour_kernel_ms.restype = C.c_double
+        L.mr_nearest_src_plan_create.argtypes = [vp, C.POINTER(mr_params), C.POINTER(mr_cell_index), C.c_uint32,
+                                                 C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(mr_cell_index), C.c_uint32,
+                                                 C.c_uint32, C.POINTER(vp)]
+        L.mr_nearest_src_plan_create.restype = C.c_int
+        L.mr_nearest_src_records.argtypes = [vp, vp, C.c_uint64]
+        L.mr_nearest_src_records.restype = C.c_int
+        L.mr_nearest_src_device_records.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.mr_nearest_src_device_records.restype = C.c_int
+        L.mr_nearest_src_record_pitch.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.mr_nearest_src_record_pitch.restype = C.c_int
+        L.mr_nearest_src_label.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(mr_result), C.POINTER(mr_command),
+                                           C.c_uint32]
+        L.mr_nearest_src_label.restype = C.c_int
+        L.mr_nearest_src_segmentation.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4
+        L.mr_nearest_src_segmentation.restype = C.c_int
+        L.mr_nearest_src_kernel_ms.argtypes = [vp]
+        L.mr_nearest_src_kernel_ms.restype = C.c_double
         _lib = L
     return _lib
 
@@ -422,6 +441,24 @@ class FindPath:
         plan = TourPlan(self.grid, self.params(), tours, mode)
         plan.run()
         return plan.records()
+
+    def eval_nearest_source(self, sources: Sequence[CellIndex], dests: Sequence[CellIndex],
+                            groups: Optional[Sequence[int]] = None, worst: bool = False):
+        """Per destination and group of sources the best (worst=True: the worst) listed source
+        after one pass of a NearestSourcePlan: its records(), (n_dst, n_groups, 5) uint32."""
+        plan = NearestSourcePlan(self.grid, self.params(), sources, dests, groups,
+                                 which=abi.SRC_WORST if worst else abi.SRC_BEST)
+        plan.run()
+        return plan.records()
+
+    def eval_rally(self, members: Sequence[CellIndex], candidates: Sequence[CellIndex]):
+        """Where to meet so that the last to arrive gets there soonest: (j, record) of the
+        candidate j whose worst member has the least (m[q0], m[q1], m[q2], j) in the parameters'
+        metric order; record is that member's (legs, money, time, via, position in members)."""
+        rec = self.eval_nearest_source(members, candidates, worst=True)[:, 0, :]
+        q = metric_order(self.params())
+        j = min(range(len(candidates)), key=lambda c: (int(rec[c, q[0]]), int(rec[c, q[1]]), int(rec[c, q[2]]), c))
+        return j, rec[j]
 
     def eval_batch_raw(self, pairs: Sequence[Tuple[CellIndex, CellIndex]]):
         n = len(pairs)
@@ -1074,3 +1111,110 @@ class TourPlan(Plan):
 
     def fetch(self):
         raise NotImplementedError("tour plans: use records() / leg()")
+
+
+def metric_order(params: Params) -> Tuple[int, int, int]:
+    """(q0, q1, q2): the parameters' metric order over (legs, money, time), sort_by completed as
+    the comparator completes it (a repeated key gives way to time after legs, to legs otherwise;
+    the metric not listed comes last)."""
+    col = {abi.SORT_LEGS: 0, abi.SORT_MONEY: 1, abi.SORT_TIME: 2}
+    s1, s2 = (int(x) for x in params.sort_by)
+    if s1 == s2:
+        s2 = abi.SORT_TIME if s1 == abi.SORT_LEGS else abi.SORT_LEGS
+    return col[s1], col[s2], 3 - col[s1] - col[s2]
+
+
+class NearestSourcePlan(Plan):
+    """Nearest source: run() keeps, for every destination and group of sources, the 32 B record of
+    the group's best source (which=abi.SRC_BEST: the least metrics in the parameters' order) or
+    its worst (abi.SRC_WORST: the greatest), ties to the smallest position in `sources`, and
+    which source it was (mr_nearest_src_plan_create); label(j, g) rebuilds its full TotalCost."""
+
+    def __init__(self, grid: MapGrid, params: Params, sources: Sequence[CellIndex], dests: Sequence[CellIndex],
+                 groups: Optional[Sequence[int]] = None, n_groups: Optional[int] = None, which: int = abi.SRC_BEST):
+        self.grid = grid
+        self.n = len(sources)
+        self.n_dst = len(dests)
+        self.sources = list(sources)
+        self.dests = list(dests)
+        self.groups = None if groups is None else [int(g) for g in groups]
+        if self.groups is not None and len(self.groups) != self.n:
+            raise EngineError(abi.MR_ERR_INVALID_ARG, "groups: one id per source")
+        if n_groups is None:
+            n_groups = 1 if self.groups is None else max(self.groups, default=0) + 1
+        self.n_groups = n_groups
+        self.which = which
+        if not 0 <= int(which) <= 0xFFFFFFFF:
+            raise EngineError(abi.MR_ERR_INVALID_ARG, "which: an MR_SRC_* value")
+        self._p = params.to_c()
+        garr = None
+        if self.groups is not None:
+            if any(g < 0 or g > 0xFFFFFFFF for g in self.groups):
+                raise EngineError(abi.MR_ERR_INVALID_ARG, "groups: ids are unsigned 32-bit")
+            garr = (C.c_uint32 * max(self.n, 1))(*self.groups)
+        h = C.c_void_p()
+        st = lib().mr_nearest_src_plan_create(grid.handle, C.byref(self._p), _cell_array(sources), self.n, garr,
+                                              self.n_groups, _cell_array(dests), self.n_dst, int(which), C.byref(h))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        self.handle = h
+
+    def records(self):
+        """(n_dst, n_groups, 5) uint32 array: legs, money, time, via and the winner's position in
+        `sources` (abi.SRC_NONE for an empty group) of destination j x group g."""
+        import numpy as np
+        out = np.empty((self.n_dst, self.n_groups, 8), dtype=np.uint32)
+        st = lib().mr_nearest_src_records(self.handle, out.ctypes.data, self.n_dst * self.n_groups)
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return np.ascontiguousarray(out[:, :, :5])
+
+    def device_records(self):
+        """(device pointer, bytes) of the records: [group][record_pitch()] records of 32 B."""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        st = lib().mr_nearest_src_device_records(self.handle, C.byref(ptr), C.byref(n))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return ptr.value, n.value
+
+    def record_pitch(self) -> int:
+        """Records per group of device_records() (n_dst rounded up to a multiple of 4)."""
+        p = C.c_uint32()
+        st = lib().mr_nearest_src_record_pitch(self.handle, C.byref(p))
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return p.value
+
+    def label(self, j: int, g: int = 0) -> Optional[TotalCost]:
+        """The full label of the winner of destination j x group g, or None for an empty group."""
+        res = mr_result()
+        cap = 64
+        while True:
+            cmds = (mr_command * cap)()
+            st = lib().mr_nearest_src_label(self.handle, j, g, C.byref(res), cmds, cap)
+            if st == MR_ERR_CAPACITY and res.n_commands > cap:
+                cap = res.n_commands
+                continue
+            break
+        if st == MR_NOT_FOUND:
+            return None
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        res.command_offset = 0
+        return result_from_c(res, cmds)
+
+    def segmentation(self) -> dict:
+        """How the plan cut its groups (mr_nearest_src_segmentation): seg_len, and the groups
+        reduced whole, split into several segments, and ending exactly on a segment edge."""
+        v = [C.c_uint32() for _ in range(4)]
+        st = lib().mr_nearest_src_segmentation(self.handle, *[C.byref(x) for x in v])
+        if st != MR_OK:
+            raise EngineError(st, last_error())
+        return dict(zip(("seg_len", "whole", "split", "on_edge"), (x.value for x in v)))
+
+    def reduce_ms(self) -> float:
+        """Average time of a pass's reduction launches over the window the last kernel_ms() closed."""
+        return lib().mr_nearest_src_kernel_ms(self.handle)
+
+    def fetch(self):
+        raise NotImplementedError("nearest-source plans: use records() / label()")
