@@ -357,7 +357,11 @@ enum {
 int mr_plan_get_stats(mr_plan *plan, mr_plan_stats *out);
 /* Average device time (ms) of the main solve kernel over the last
  * mr_plan_run calls since the previous call to this function, measured with
- * HIP events on the stream the kernel is launched on. */
+ * HIP events on the stream the kernel is launched on.  A pass that is exactly one
+ * launch (a query plan's passes once one of them had no fallback source) carries its
+ * pair on the dispatch: the time is then the dispatch's own begin to its end.  Every
+ * other pass is timed by two events recorded round its launches, which also count the
+ * gaps between them and the records' own processing. */
 double mr_plan_kernel_ms(mr_plan *plan, uint32_t *n_launches);
 /* Frees the device blocks the engine keeps for reuse by later plans (plan buffers go
  * back to a per-device cache of up to 16 GiB when a plan is destroyed, so creating the

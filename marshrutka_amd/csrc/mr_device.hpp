@@ -60,6 +60,14 @@ inline int occupancy_cached(const void *fn, int bs, size_t lds) {
     cache.emplace(key, n);
     return n;
 }
+// A launch of a pass's kernel.  timed: null, or the pass's pair of events {start, stop} where
+// the pass is this one launch (mr_plan_run): the pair is then bound to the dispatch itself,
+// its begin and its end, instead of being recorded round it as two commands of their own.
+inline hipError_t launch_pass(const void *fn, dim3 grid, dim3 block, void **args, size_t lds, hipStream_t stream,
+                              const hipEvent_t *timed) {
+    if (timed) return hipExtLaunchKernel(fn, grid, block, args, lds, stream, timed[0], timed[1], 0);
+    return hipLaunchKernel(fn, grid, block, args, lds, stream);
+}
 constexpr uint32_t kOwn = 0xFFFFu;
 constexpr uint32_t kNone32 = 0xFFFFFFFFu;
 constexpr unsigned long long kInf64 = ~0ull;

@@ -33,7 +33,7 @@ hipError_t launch_solve(const KArgs *d_args, bool grid_in_lds, uint32_t algo, ui
 int max_blocks_per_cu(bool grid_in_lds, uint32_t algo, uint32_t bytes);
 uint32_t hub_lds_bytes(uint32_t NS, uint32_t nreg, uint32_t spw);
 hipError_t launch_hub(const KArgs *d_args, const uint32_t perm[3], uint32_t spw, bool nonlin, uint32_t NS, uint32_t nreg,
-                      uint32_t blocks, hipStream_t stream);
+                      uint32_t blocks, hipStream_t stream, const hipEvent_t *timed = nullptr);
 hipError_t launch_fill(const KArgs *d_args, const uint32_t perm[3], uint32_t gx, uint32_t gy, hipStream_t stream);
 int hub_blocks_per_cu(const uint32_t perm[3], uint32_t spw, bool nonlin, uint32_t bytes);
 int fill_blocks_per_cu(const uint32_t perm[3]);
@@ -56,11 +56,11 @@ int hub_fill_blocks_per_cu(const uint32_t perm[3], uint32_t spw, uint32_t lds_by
 uint32_t hub_wide_lds_bytes(uint32_t NS, uint32_t nreg);
 uint32_t hub_wide_spl(uint32_t NS);
 hipError_t launch_hub_wide(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t blocks,
-                           hipStream_t stream);
+                           hipStream_t stream, const hipEvent_t *timed = nullptr);
 int hub_wide_blocks_per_cu(const uint32_t perm[3], uint32_t NS, uint32_t bytes);
 uint32_t hub_lane_entries(uint32_t NS);
 hipError_t launch_hub_lane(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
-                           bool nonlin, hipStream_t stream);
+                           bool nonlin, hipStream_t stream, const hipEvent_t *timed = nullptr);
 uint32_t lane_memo_words(uint32_t NS, uint32_t nreg);
 hipError_t launch_lane_memo_build(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg,
                                   hipStream_t stream);
@@ -68,11 +68,13 @@ hipError_t launch_lane_win_build(const KArgs *d_args, const uint32_t perm[3], ui
                                  hipStream_t stream);
 uint32_t lane_stage_max_cmds();
 hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
-                                bool win, bool stage, uint32_t lds_pad, hipStream_t stream);
+                                bool win, bool stage, uint32_t lds_pad, hipStream_t stream,
+                                const hipEvent_t *timed = nullptr);
 hipError_t launch_lane_query_expand(const uint32_t *src_v, const uint32_t *q_begin, uint32_t n_lane, uint32_t *q_srcv,
                                     hipStream_t stream);
 hipError_t launch_hub_lane_query(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t nq_lane,
-                                 uint32_t grid_cap, uint32_t lds_pad, hipStream_t stream);
+                                 uint32_t grid_cap, uint32_t lds_pad, hipStream_t stream,
+                                 const hipEvent_t *timed = nullptr);
 uint32_t hub_group_slots(uint32_t NS, uint32_t G);
 uint32_t lane_blob_build(const SpecialStatic *sp, uint32_t NS, uint32_t nreg, uint32_t TM, uint32_t rgt,
                          uint32_t ff_num, uint32_t ff_den, const uint32_t *near_sp, std::vector<uint32_t> &blob);
@@ -93,7 +95,7 @@ hipError_t partition_sources_device(uint32_t n, uint32_t V, uint32_t ns, uint32_
                                     uint32_t *qd2, uint32_t *qi2, hipStream_t s);
 uint32_t hub_group_lds_bytes(uint32_t NS, uint32_t nreg, uint32_t G);
 hipError_t launch_hub_group(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n,
-                            uint32_t G, bool nonlin, hipStream_t stream);
+                            uint32_t G, bool nonlin, hipStream_t stream, const hipEvent_t *timed = nullptr);
 hipError_t launch_cert_select(const KArgs *d_args, hipStream_t stream);
 hipError_t launch_cert_check(const KArgs *d_args, uint32_t gx, uint32_t slots, uint32_t mark, hipStream_t stream);
 hipError_t launch_cert_sweep(const KArgs *d_args, uint32_t slots, hipStream_t stream);
@@ -1634,6 +1636,7 @@ struct mr_plan {
         Event first, second;
     };
     std::vector<TimedPass> timed;  // pending event pairs
+    std::vector<Event> ev_free;    // events of folded pairs, for the next passes' pairs (at most 2 kMaxTimed)
     // second: the pass's end event (owned by `timed`); whole: the pass is the fill launch
     // (the pass pair times it)
     struct FillTimed {
@@ -2968,9 +2971,11 @@ extern "C" int mr_plan_create_ex(const mr_grid *g, const mr_params *prm, const m
 
 
 
-static hipError_t launch_hub_plan(const mr_plan *pl, const KArgs *d_args, hipStream_t s) {
-    if (pl->hp.wide) return launch_hub_wide(d_args, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->hub.hub_blocks, s);
-    return launch_hub(d_args, pl->ka.p.perm, pl->hub.spw, pl->hp.nonlin, pl->ka.p.NS, pl->ka.nreg, pl->hub.hub_blocks, s);
+// (one launch either way; timed: the pass's event pair where this launch is the whole pass)
+static hipError_t launch_hub_plan(const mr_plan *pl, const KArgs *d_args, hipStream_t s, const hipEvent_t *timed = nullptr) {
+    if (pl->hp.wide) return launch_hub_wide(d_args, pl->ka.p.perm, pl->ka.p.NS, pl->ka.nreg, pl->hub.hub_blocks, s, timed);
+    return launch_hub(d_args, pl->ka.p.perm, pl->hub.spw, pl->hp.nonlin, pl->ka.p.NS, pl->ka.nreg, pl->hub.hub_blocks, s,
+                      timed);
 }
 static hipError_t launch_fallback(const mr_plan *pl, const mr_plan::Slot &k, hipStream_t s) {
     return launch_solve(k.args_fb.get(), pl->grid_in_lds, pl->algo, pl->ka.p.NS, pl->ka.p.V, pl->hub.fb_blocks, s);
@@ -3089,7 +3094,9 @@ static hipError_t cert_repair(const mr_plan *pl, const KArgs *args, hipStream_t 
 // inputs, deterministic result) had no fallback source, the hub launches end the pass on
 // their own.  (A Fleetfoot lane plan relaunches hub_kernel for the sources its lane kernel
 // relisted, until a pass had none.)
-static hipError_t run_hub(mr_plan *pl, hipStream_t s) {
+// timed: the pass's event pair where the pass is one launch (single_launch_pass), which then
+// carries the pair; null: the caller records the pair round the pass.
+static hipError_t run_hub(mr_plan *pl, hipStream_t s, const hipEvent_t *timed) {
     const mr_plan::Hub &h = pl->hub;
     const mr_plan::Cert &c = pl->cert;
     const mr_plan::Slot &k = pl->cur();
@@ -3100,12 +3107,13 @@ static hipError_t run_hub(mr_plan *pl, hipStream_t s) {
     if (h.n_lane) {
         const KArgs *la = (pl->fb_none && !big ? h.args_lane_last : h.args_lane).get();
         // (a plan whose memo gate held: the destinations only, from the grid's rows)
-        if (h.lane_g) e = launch_hub_group(la, perm, NS, nreg, h.n_lane, h.lane_g, pl->hp.nonlin, s);
-        else if (h.lane_query) e = launch_hub_lane_query(la, perm, NS, nreg, h.nq_lane, h.lane_query_grid, h.lane_lds_pad, s);
-        else if (pl->ka.lane_memo) e = launch_hub_lane_memo(la, perm, NS, nreg, h.n_lane, pl->ka.lane_win != nullptr, h.lane_stage, h.lane_lds_pad, s);
-        else e = launch_hub_lane(la, perm, NS, nreg, h.n_lane, pl->hp.nonlin, s);
+        if (h.lane_g) e = launch_hub_group(la, perm, NS, nreg, h.n_lane, h.lane_g, pl->hp.nonlin, s, timed);
+        else if (h.lane_query) e = launch_hub_lane_query(la, perm, NS, nreg, h.nq_lane, h.lane_query_grid, h.lane_lds_pad, s, timed);
+        else if (pl->ka.lane_memo) e = launch_hub_lane_memo(la, perm, NS, nreg, h.n_lane, pl->ka.lane_win != nullptr, h.lane_stage, h.lane_lds_pad, s, timed);
+        else e = launch_hub_lane(la, perm, NS, nreg, h.n_lane, pl->hp.nonlin, s, timed);
     }
-    if (e == hipSuccess && big) e = launch_hub_plan(pl, pl->fb_none ? h.args_hub_last.get() : args, s);
+    // (a timed pair went to the lane launch above, or goes to this one: never both, single_launch_pass)
+    if (e == hipSuccess && big) e = launch_hub_plan(pl, pl->fb_none ? h.args_hub_last.get() : args, s, h.n_lane ? nullptr : timed);
     // certified fallback: the slots given to the staged sources in source order,
     // their closed forms, the check, one repair sweep, the check again (each exits at
     // once without slots); the SSSP launch then
@@ -3163,13 +3171,37 @@ static hipError_t run_nearest_src(mr_plan *pl, hipStream_t s) {
     return e;
 }
 
+// Whether the next pass of the plan is exactly one kernel launch, known before it is
+// launched: a hub query plan that has seen a pass without fallback sources (so no
+// certificate, no SSSP launch and no relisting), whose sources are all the lane kernel's or
+// all the hub kernel's, and nothing behind it (no pool reorder; tours and nearest-source
+// plans are all-destinations plans).  run_hub's launches, read against its conditions.
+static bool single_launch_pass(const mr_plan *pl) {
+    if (!pl->hp.hub || pl->all_mode || !pl->fb_none) return false;
+    if (pl->out.ovf_order || pl->tour || pl->nsrc) return false;
+    const mr_plan::Hub &h = pl->hub;
+    return h.n_lane == 0 || pl->ka.nsrc <= h.n_lane;  // (big, with fb_none: nsrc > n_lane)
+}
+
+// an event for a pass's pair: one that fold_timed put back, else a new one
+static Event pass_event(mr_plan *pl) {
+    Event e;
+    if (!pl->ev_free.empty()) {
+        e = std::move(pl->ev_free.back());
+        pl->ev_free.pop_back();
+    } else {
+        (void)e.create();
+    }
+    return e;
+}
+
 extern "C" int mr_plan_run(mr_plan *pl, void *stream) {
     if (!pl) return fail(MR_ERR_INVALID_ARG, "null plan");
     hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : pl->stream.get();
     if (pl->ka.nsrc == 0) return MR_OK;
     if (pl->timed.size() >= kMaxTimed) fold_timed(pl, kMaxTimed / 4);
-    Event e0, e1;
-    if (e0.create() != hipSuccess || e1.create() != hipSuccess) return fail(MR_ERR_DEVICE, "event");
+    Event e0 = pass_event(pl), e1 = pass_event(pl);
+    if (!e0 || !e1) return fail(MR_ERR_DEVICE, "event");
     // Passes of one plan run in submission order whatever streams they are given:
     // a pass reads what the previous one left (the fused look-ahead tables, the
     // counters it resets, a slot the previous fill read), so a pass on another stream
@@ -3189,19 +3221,28 @@ extern "C" int mr_plan_run(mr_plan *pl, void *stream) {
         pl->slot = pl->next_slot();
         k.used = true;
     }
-    (void)hipEventRecord(e0.get(), s);
+    // A pass of one launch carries its pair on the dispatch (hipExtLaunchKernel): the pair
+    // then spans the dispatch's own begin and end, and the stream holds one command, not
+    // three.  Every other pass has the pair recorded round it.  (Events without flags
+    // either way: what a wait on the end event orders is the same.)
+    const bool bound = single_launch_pass(pl);
+    const hipEvent_t pair[2] = {e0.get(), e1.get()};
+    if (!bound) (void)hipEventRecord(e0.get(), s);
     ++pl->runs;
     hipError_t e;
     if (all_hub && pl->fused) e = run_fused(pl, prev_slot, s);
     else if (all_hub) e = run_all(pl, s);
-    else if (pl->hp.hub) e = run_hub(pl, s);
+    else if (pl->hp.hub) e = run_hub(pl, s, bound ? pair : nullptr);
     else e = launch_solve(pl->cur().args.get(), pl->grid_in_lds, pl->algo, pl->ka.p.NS, pl->ka.p.V, pl->blocks, s);
     // raw outputs for a collective: the overflow pool in record order (byte-deterministic)
     if (e == hipSuccess && pl->out.ovf_order && !pl->all_mode)
         e = launch_ovf_order(pl->cur().args.get(), nrec_of(pl->hp), pl->out.ovf_tmp.get(), s);
     if (e == hipSuccess && pl->tour) e = run_tours(pl, s);
     if (e == hipSuccess && pl->nsrc) e = run_nearest_src(pl, s);
-    (void)hipEventRecord(e1.get(), s);
+    // (a bound pass whose launch failed left its pair unrecorded: recorded here, the end
+    // event still stands behind everything the stream holds)
+    if (bound && e != hipSuccess) (void)hipEventRecord(e0.get(), s);
+    if (!bound || e != hipSuccess) (void)hipEventRecord(e1.get(), s);
     // the pass's end event doubles as the plan's last event (plan_sync): a record of
     // its own cost ~6 us of command-processor time per pass.  `timed` owns it from here.
     pl->ev_last_keep = Event();
@@ -3270,8 +3311,11 @@ static void fold_timed(mr_plan *pl, size_t keep) {
             pl->acc_ms += ms;
             ++pl->acc_n;
         }
-        // plan_sync still waits on the last pass's end event: the plan keeps that one
+        // plan_sync still waits on the last pass's end event: the plan keeps that one; the
+        // others, waited for above, go back to mr_plan_run
         if (e.second.get() == pl->ev_last) pl->ev_last_keep = std::move(e.second);
+        else pl->ev_free.push_back(std::move(e.second));
+        pl->ev_free.push_back(std::move(e.first));
     }
     pl->timed.erase(pl->timed.begin(), pl->timed.begin() + ptrdiff_t(n));
 }

@@ -364,10 +364,20 @@ __device__ __forceinline__ void quad_transpose(uint32_t (&x)[4]) {
 }
 // (kLaneQuery) 16 bytes through a buffer descriptor at a byte offset; kLaneDrop: an offset
 // past the end of every buffer emit_q describes, for a lane that stores nothing
+// POLICY: the store's cache policy, the builtin's encoding on gfx950 (0 plain, 1 sc0, 2 nt,
+// 16 sc1, 17 sc0 sc1, 18 nt sc1)
 constexpr uint32_t kLaneDrop = 0x40000000u;
+template <int POLICY>
 __device__ __forceinline__ void bstore16(__amdgpu_buffer_rsrc_t r, uint32_t off, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4{x, y, z, w}, r, int(off), 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(u32x4{x, y, z, w}, r, int(off), 0, POLICY);
 }
+// (kLaneQuery) the policy of a chunk's record stores (emit_q's block).  The records are
+// written once and not read by the kernel: with sc1 their lines do not stay in the L2, which
+// then keeps the two gather tables beside the write stream (DESIGN.md section 3a''': 16
+// against 0, 17 and 2, -DMR_LANE_QUERY_STORE=<policy> for the A/B)
+#ifndef MR_LANE_QUERY_STORE
+#define MR_LANE_QUERY_STORE 16
+#endif
 
 template <uint32_t PERM, uint32_t TM, bool NL = false, uint32_t MODE = kLaneSolve>
 struct LaneHub {
@@ -1122,7 +1132,7 @@ struct LaneHub {
         const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc(a->out_res + q0, 0, int(nrec * 16u), 0x00020000);
         const __amdgpu_buffer_rsrc_t rcmd =
             __builtin_amdgcn_make_buffer_rsrc(a->out_cmd + (unsigned long long)q0 * mc, 0, int(nrec * mc * 16u), 0x00020000);
-        bstore16(rres, skip ? kLaneDrop : lane * 16u, legs, money, time, word);
+        bstore16<MR_LANE_QUERY_STORE>(rres, skip ? kLaneDrop : lane * 16u, legs, money, time, word);
         // Rows of kLaneRowSlots slots (64 bytes) leave whole: the lanes of a quad exchange
         // their rows' slots (quad_transpose), so that in store s lane i of quad g holds slot i
         // of the record of the quad's lane s, and the quad's four lanes write that record's
@@ -1144,7 +1154,7 @@ struct LaneHub {
             const uint32_t rec = (lane & ~3u) | s;  // (whole: the record whose row this lane helps to store)
             const uint32_t drop = msel(whole, vmask(((nomask >> (rec & 63u)) & 1ull) != 0), vmask(norow || !fixed || s >= mc));
             const uint32_t off = msel(whole, rec * (kLaneRowSlots * 16u) + (lane & 3u) * 16u, (lane * mc + s) * 16u);
-            bstore16(rcmd, msel(drop, kLaneDrop, off), msel(whole, tk[s], rk[s]), msel(whole, tf[s], rf[s]), msel(whole, tt[s], rt[s]), 0u);
+            bstore16<MR_LANE_QUERY_STORE>(rcmd, msel(drop, kLaneDrop, off), msel(whole, tk[s], rk[s]), msel(whole, tf[s], rf[s]), msel(whole, tt[s], rt[s]), 0u);
         }
         MR_LSTAMP(3);  // (3 in this mode: the label's walk and the record's stores)
         return skip ? 0u : 1u;

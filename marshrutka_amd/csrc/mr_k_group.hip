@@ -34,7 +34,7 @@ uint32_t hub_group_lds_bytes(uint32_t NS, uint32_t nreg, uint32_t G) {
 }
 
 hipError_t launch_hub_group(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n,
-                            uint32_t G, bool nonlin, hipStream_t stream) {
+                            uint32_t G, bool nonlin, hipStream_t stream, const hipEvent_t *timed) {
     const uint32_t k = perm[0] * 9 + perm[1] * 3 + perm[2];
     const uint32_t E = hub_group_slots(NS, G);
     const void *fn = nullptr;
@@ -48,7 +48,7 @@ hipError_t launch_hub_group(const KArgs *d_args, const uint32_t perm[3], uint32_
     if (bytes > 64u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
     const uint32_t per_block = kBS / G, blocks = (n + per_block - 1u) / per_block;
     void *args[] = {const_cast<KArgs **>(&d_args)};
-    return hipLaunchKernel(fn, dim3(blocks ? blocks : 1u), dim3(kBS), args, bytes, stream);
+    return launch_pass(fn, dim3(blocks ? blocks : 1u), dim3(kBS), args, bytes, stream, timed);
 }
 
 }  // namespace mr

@@ -15,13 +15,13 @@ static const void *hub_fn(const uint32_t perm[3], uint32_t spw, bool nonlin) {
 }
 
 hipError_t launch_hub(const KArgs *d_args, const uint32_t perm[3], uint32_t spw, bool nonlin, uint32_t NS,
-                      uint32_t nreg, uint32_t blocks, hipStream_t stream) {
+                      uint32_t nreg, uint32_t blocks, hipStream_t stream, const hipEvent_t *timed) {
     const uint32_t bytes = hub_lds_bytes(NS, nreg, spw);
     const void *fn = hub_fn(perm, spw, nonlin);
     if (!fn) return hipErrorInvalidValue;
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
     void *args[] = {const_cast<KArgs **>(&d_args)};
-    return hipLaunchKernel(fn, dim3(blocks), dim3(kBS), args, bytes, stream);
+    return launch_pass(fn, dim3(blocks), dim3(kBS), args, bytes, stream, timed);
 }
 
 int hub_blocks_per_cu(const uint32_t perm[3], uint32_t spw, bool nonlin, uint32_t bytes) {

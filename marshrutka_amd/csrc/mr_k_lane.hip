@@ -120,14 +120,14 @@ uint32_t hub_lane_lds_bytes(uint32_t NS, uint32_t nreg) {
 }
 
 hipError_t launch_hub_lane(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
-                           bool nonlin, hipStream_t stream) {
+                           bool nonlin, hipStream_t stream, const hipEvent_t *timed) {
     const void *fn = lane_fn(perm, NS, nonlin);
     if (!fn) return hipErrorInvalidValue;
     const uint32_t bytes = hub_lane_lds_bytes(NS, nreg);
     if (bytes > 64u * 1024u) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
     const uint32_t waves = (n_lane + 63u) / 64u, blocks = (waves + 3u) / 4u;
     void *args[] = {const_cast<KArgs **>(&d_args)};
-    return hipLaunchKernel(fn, dim3(blocks ? blocks : 1u), dim3(kBS), args, bytes, stream);
+    return launch_pass(fn, dim3(blocks ? blocks : 1u), dim3(kBS), args, bytes, stream, timed);
 }
 
 }  // namespace mr

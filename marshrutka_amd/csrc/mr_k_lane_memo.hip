@@ -260,7 +260,7 @@ uint32_t lane_stage_max_cmds() { return kLaneStageSlots; }
 // rows leave through the stage (max_cmds 1 .. lane_stage_max_cmds()).  lds_pad: bytes of
 // LDS the kernel does not use, which hold it to fewer workgroups a CU (occupancy scans)
 hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t n_lane,
-                                bool win, bool stage, uint32_t lds_pad, hipStream_t stream) {
+                                bool win, bool stage, uint32_t lds_pad, hipStream_t stream, const hipEvent_t *timed) {
     const uint32_t pi = perm[0] * 9 + perm[1] * 3 + perm[2];
     const void *fn = stage ? hub_lane_stage_kernel_fn(pi) : win ? hub_lane_read_kernel_fn(pi) : hub_lane_memo_kernel_fn(pi);
     if (!fn || NS + 1 > 22 || (stage && !win)) return hipErrorInvalidValue;
@@ -268,7 +268,7 @@ hipError_t launch_hub_lane_memo(const KArgs *d_args, const uint32_t perm[3], uin
     if (bytes > 64u * 1024u) return hipErrorInvalidValue;
     const uint32_t waves = (n_lane + 63u) / 64u, blocks = (waves + 3u) / 4u;
     void *args[] = {const_cast<KArgs **>(&d_args)};
-    return hipLaunchKernel(fn, dim3(blocks ? blocks : 1u), dim3(kBS), args, bytes, stream);
+    return launch_pass(fn, dim3(blocks ? blocks : 1u), dim3(kBS), args, bytes, stream, timed);
 }
 
 // KArgs::q_srcv of a plan: a thread per lane source writes its cell over its records
@@ -314,7 +314,7 @@ static uint32_t resident_workgroups(const void *fn, uint32_t bytes) {
 // (diagnostic, MR_LANE_QUERY_GRID): at most this many workgroups, 0: no cap; kNone32: a
 // workgroup per 256 records whatever is resident (every wave takes one chunk)
 hipError_t launch_hub_lane_query(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t nq_lane,
-                                 uint32_t grid_cap, uint32_t lds_pad, hipStream_t stream) {
+                                 uint32_t grid_cap, uint32_t lds_pad, hipStream_t stream, const hipEvent_t *timed) {
     const void *fn = hub_lane_query_kernel_fn(perm[0] * 9 + perm[1] * 3 + perm[2]);
     if (!fn || NS + 1 > 22) return hipErrorInvalidValue;
     const uint32_t bytes = lane_memo_lds_bytes(NS, nreg, 22) + lds_pad;
@@ -337,7 +337,7 @@ hipError_t launch_hub_lane_query(const KArgs *d_args, const uint32_t perm[3], ui
         }
     }
     void *args[] = {const_cast<KArgs **>(&d_args)};
-    return hipLaunchKernel(fn, dim3(blocks), dim3(kBS), args, bytes, stream);
+    return launch_pass(fn, dim3(blocks), dim3(kBS), args, bytes, stream, timed);
 }
 
 }  // namespace mr

@@ -26,13 +26,13 @@ static const void *wide_fn(const uint32_t perm[3], uint32_t NS) {
     }
 }
 hipError_t launch_hub_wide(const KArgs *d_args, const uint32_t perm[3], uint32_t NS, uint32_t nreg, uint32_t blocks,
-                           hipStream_t stream) {
+                           hipStream_t stream, const hipEvent_t *timed) {
     const uint32_t bytes = hub_wide_lds_bytes(NS, nreg);
     const void *fn = wide_fn(perm, NS);
     if (!fn) return hipErrorInvalidValue;
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
     void *args[] = {const_cast<KArgs **>(&d_args)};
-    return hipLaunchKernel(fn, dim3(blocks), dim3(kBS), args, bytes, stream);
+    return launch_pass(fn, dim3(blocks), dim3(kBS), args, bytes, stream, timed);
 }
 int hub_wide_blocks_per_cu(const uint32_t perm[3], uint32_t NS, uint32_t bytes) {
     int n = 0;
